@@ -10,11 +10,21 @@ A step = one forward of one batch of synthetic hazy tensors already resident in 
 libcfen_hip.so (replayed from a hipGraph).  Consecutive steps rotate over --in-flight launch plans (own workspace
 and output slab, shared weights) on as many streams, so several forwards are in flight at once (default: 4 on one
 GPU, 3 per rank beside the all-gather stream; one hardware queue per stream: GPU_MAX_HW_QUEUES=8 is exported below);
-all K steps complete inside the timed region, and the same line reports ONE forward at a time as well
+all K steps complete inside the timed region, and with --full the same line reports ONE forward at a time as well
 (pipelining.one_forward_in_flight).  With N > 1 every rank runs its own 8 images (weak scaling,
 weights replicated) and the per-rank output slab is all-gathered with RCCL; the gather of step i is launched from
 the lane that ran step i and overlaps the forwards of the other lanes; the last ones are waited for inside the timed region.
 Rank 0 prints ONE JSON line.
+
+A plain run does what its headline needs and nothing else: set up, --warmup steps, ONE timed region of exactly --steps steps
+(`ms_per_step` = that region / --steps; --min-seconds S repeats the region until S seconds are timed and reports the median), the
+outputs of the last timed step when --dump-outputs DIR is given, the result line.  --full adds everything else the benchmark measures
+or checks: the one-forward-in-flight leg, the per-kernel profile and roofline, the self-check against tests/golden, the optional legs
+(BASELINE configs 4 / 5, exact fp32, the gather overhead) and the CPU baseline.
+
+--dump-outputs DIR writes what the caller of the timed path receives from its last step -- xr, xs, xd of the batch (all ranks' images
+with N > 1, as gathered) -- as DIR/<name>.npy in float32: whole arrays when they fit in 64 MB together (the headline does), otherwise
+the same seeded sample of every array.  Weights and inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -179,6 +189,23 @@ def pmc_traffic(kernel):
     return None
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outs, names, path, seed=0):
+    """<path>/<name>.npy (float32) for every output tensor: whole when they fit in DUMP_BUDGET_BYTES together, else a seeded
+    sample of each -- the sorted distinct flat indices of rng(seed).integers, the same for the same shapes -- so the files stay comparable run to run"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    frac = min(1.0, DUMP_BUDGET_BYTES / float(4 * sum(o.numel() for o in outs)))
+    rng = np.random.default_rng(seed)
+    for nm, o in zip(names, outs):
+        if frac < 1.0:
+            idx = np.unique(rng.integers(0, o.numel(), int(o.numel() * frac)))
+            o = o.reshape(-1)[torch.from_numpy(idx).to(o.device)]
+        np.save(os.path.join(path, nm + ".npy"), o.float().cpu().numpy())
+
+
 def apply_tuning():
     """CFEN_TUNE="key=value,..." -> cfen_tune (kernel-variant experiments; unset = shipped defaults)"""
     spec = os.environ.get("CFEN_TUNE", "")
@@ -198,8 +225,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="the K-step timed region is repeated until this much time has been measured; value = median repetition")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="repeat the K-step timed region until this much time has been measured; value = median repetition (default: one region)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32"])
@@ -218,9 +245,13 @@ def main():
                     help="launch plan of one forward: 2 = GViT beside LViT on a second graph branch, 1 = one serial chain of launches; 0 (default) = 1 when "
                          "several forwards are in flight (measured: 2.26 against 2.38 ms per step -- the forwards overlap each other, and a branch in "
                          "every graph costs ~0.05 ms of cross-queue synchronisation per level), 2 for --in-flight 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also the one-forward leg, per-kernel profile and roofline, self-check against tests/golden, optional legs and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/{xr,xs,xd}.npy (float32, <= 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the short timed legs of BASELINE configs 4 (batch 4, 1024x1024) and 5 (batch 16, hidden_dim_ratio 2) in the default run")
+                    help="skip the short timed legs of BASELINE configs 4 (batch 4, 1024x1024) and 5 (batch 16, hidden_dim_ratio 2) in the --full run")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--brief", action="store_true",
                     help="a leg of another run: the timed region and the self-check only (no per-launch profile, no one-forward leg), a compact result line")
@@ -422,12 +453,14 @@ def main():
             dt = float(t.item())
         return dt
 
-    # a 20-step region is 70 ms: clock ramp and launch jitter dominate it.  The region is repeated (every repetition is the
-    # contract's K-step measurement) until >= --min-seconds have been timed; the reported value is the MEDIAN repetition.
+    # exactly --steps timed steps by default.  A 20-step region is 70 ms: clock ramp and launch jitter dominate it, so --min-seconds S repeats the
+    # region (every repetition is the contract's K-step measurement) until >= S seconds have been timed; the reported value is then the MEDIAN repetition.
+    min_seconds = args.min_seconds or 0.0
+    leg_seconds = 0.4 if args.min_seconds is None else min(0.4, args.min_seconds)       # the one-forward leg and the optional legs of --full
     reps = [timed_region()]
-    while sum(reps) < args.min_seconds and len(reps) < 200:
+    while sum(reps) < min_seconds and len(reps) < 200:
         if dist is not None:          # all ranks must agree on the number of repetitions
-            flag = torch.tensor([1.0 if sum(reps) < args.min_seconds else 0.0], device=dev)
+            flag = torch.tensor([1.0 if sum(reps) < min_seconds else 0.0], device=dev)
             dist.all_reduce(flag, op=dist.ReduceOp.MAX)
             if flag.item() == 0:
                 break
@@ -437,8 +470,15 @@ def main():
     ms_step = dt / args.steps * 1e3
     ips = world * B * args.steps / dt
 
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received from its last step: the slab it wrote, or with a gatherer every rank's images as gathered
+        from cfen_vit_dehazing_amd.parallel import merge_gathered, split_slab
+        last = (args.steps - 1) % nslab
+        outs = merge_gathered(gather.bufs[last].float(), world, B, n) if gather is not None else split_slab(slabs[last], B, n)
+        dump_outputs(outs, ("xr", "xs", "xd"), args.dump_outputs)
+
     serial = None
-    if nfl > 1 and graphs is not None and not args.brief:
+    if args.full and nfl > 1 and graphs is not None and not args.brief:
         # ONE forward in flight, on the launch plan that is best for it (GViT beside LViT on a second graph branch): the same K-step region on the
         # default stream, >= 0.4 s, median -- reported beside the headline so that what the overlap of consecutive steps buys is visible in every run
         was_serial = net.serial_plan
@@ -451,9 +491,9 @@ def main():
         for i in range(3):
             step(i)
         sreps = [timed_region()]
-        while sum(sreps) < min(0.4, args.min_seconds) and len(sreps) < 50:
+        while sum(sreps) < leg_seconds and len(sreps) < 50:
             if dist is not None:
-                flag = torch.tensor([1.0 if sum(sreps) < min(0.4, args.min_seconds) else 0.0], device=dev)
+                flag = torch.tensor([1.0 if sum(sreps) < leg_seconds else 0.0], device=dev)
                 dist.all_reduce(flag, op=dist.ReduceOp.MAX)
                 if flag.item() == 0:
                     break
@@ -489,54 +529,6 @@ def main():
         os.write(result_fd, (json.dumps(result) + "\n").encode())
     elif rank == 0:
         flops_img = net.flops_per_image()
-        # per-kernel-class timing with HIP events on the launch stream (3 profiled forwards, median of sums)
-        profs = [net.profile(x) for _ in range(3)]
-        classes = {}
-        for name in net.KERNEL_CLASSES:
-            runs = sorted(p[name][0] for p in profs)
-            classes[name] = {"ms": round(runs[1], 4), "launches": profs[0][name][2], "gflop": round(profs[0][name][1] / 1e9, 2)}
-        peak = MFMA_PEAK_TFLOPS[args.dtype]
-        for c in classes.values():
-            c["tflops"] = round(c["gflop"] / c["ms"], 2) if c["ms"] > 0 and c["gflop"] > 0 else None
-        # per-KERNEL table from the per-launch records of the median profile: the roofline line names the dominant kernel
-        kern = {}
-        mid = sorted(profs, key=lambda p: sum(p[n][0] for n in net.KERNEL_CLASSES))[1]
-        for label, cls, fl, ms, _kn, _by in mid["launches"]:
-            k = kern.setdefault(kernel_key(label, cls), {"ms": 0.0, "gflop": 0.0, "launches": 0})
-            k["ms"] += ms; k["gflop"] += fl / 1e9; k["launches"] += 1
-        for k in kern.values():
-            k["ms"] = round(k["ms"], 4); k["gflop"] = round(k["gflop"], 2)
-            k["tflops"] = round(k["gflop"] / k["ms"], 1) if k["gflop"] > 0 and k["ms"] > 0 else None
-        # the same launches grouped by the DEVICE KERNEL that ran them (the template instantiation cfen_net_profile recorded at the launch site:
-        # every k_gemm_dma<T, 1, 3> launch of the forward is ONE entry, whatever block, level or step it served)
-        sym = {}
-        for label, cls, fl, ms, kname, nbytes in mid["launches"]:
-            k = sym.setdefault(kname, {"ms": 0.0, "gflop": 0.0, "gbyte": 0.0, "launches": 0})
-            k["ms"] += ms; k["gflop"] += fl / 1e9; k["gbyte"] += nbytes / 1e9; k["launches"] += 1
-        for k in sym.values():
-            k["ms"] = round(k["ms"], 4); k["gflop"] = round(k["gflop"], 2); k["gbyte"] = round(k["gbyte"], 4)
-            k["bound"], k["achieved"], _, k["unit"], k["frac"] = nearer_roof(k["gflop"], k["gbyte"], k["ms"], peak)
-        dom = max(sym, key=lambda k: sym[k]["ms"])                   # the device kernel the forward spends most time in
-        d = sym[dom]
-        bound, ach, rpeak, runit, rfrac = nearer_roof(d["gflop"], d["gbyte"], d["ms"], peak)
-        dom_launch_ms = d["ms"] / d["launches"]
-        whole = ips / world * flops_img / 1e12
-        from cfen_vit_dehazing_amd.parallel import split_slab
-        check = self_check(net, x, split_slab(slabs[(args.steps - 1) % nslab], B, n), cfg, args.dtype)   # what the last timed step wrote
-        if gather is not None:
-            # the GATHERED buffer of the last timed step, rank by rank: segment r must be rank r's images (synthetic_input seeds r * B ...), so its
-            # first image is checked against a batch-1 eager forward of that image computed here -- an ordering bug of the all-gather /
-            # merge_gathered on real RCCL shows up in the scaling run itself (reference analogue: nn.DataParallel's gather, v3:77-83)
-            from cfen_vit_dehazing_amd.parallel import merge_gathered
-            torch.cuda.synchronize()
-            merged = merge_gathered(gather.bufs[(args.steps - 1) % nslab].float(), world, B, n)
-            per_rank = []
-            for r in range(world):
-                xi = synthetic_input(1, cfg, seed0=r * B).to(dev)
-                one = net(xi)
-                per_rank.append(round(max(float((m[r * B:r * B + 1] - o).abs().max()) for m, o in zip(merged, one)), 6))
-            check["gathered_image0_of_rank_vs_batch1_eager"] = per_rank
-            check["ok"] = check["ok"] and all(v <= check["bar"] for v in per_rank)
         result = {
             "metric": "images/sec @512x512 n_feats=24", "value": round(ips, 2), "unit": "images/sec", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
@@ -546,59 +538,108 @@ def main():
                        "global_batch": world * B, "parallelism": "dp%d" % world, "graph": graphs is not None, "forwards_in_flight": nfl, "lanes_per_forward": 1 if net.serial_plan else 2, "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
                        "gather_dtype": (gdt if world > 1 else None), "lane_search": lane_search,
                        "gflop_per_image": round(flops_img / 1e9, 2)},
-            "roofline": {"bound": bound, "kernel": dom, "achieved": ach, "peak": rpeak, "unit": runit, "frac": rfrac,
-                         "traffic": None,
-                         "traffic_from_profiles": pmc_traffic(dom),
-                         "traffic_source": "`traffic` is not measured in this run (null); traffic_from_profiles = HBM bytes per launch of this kernel in the "
-                                           "newest committed profiles/r*_pmc_traffic.json (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                           "command, fetch x2 per the gfx950 guide)",
-                         "launch_ms": round(dom_launch_ms, 4), "launches_per_step": d["launches"],
-                         "algorithmic_gflop_per_launch": round(d["gflop"] / d["launches"], 2),
-                         "algorithmic_gbyte_per_launch": round(d["gbyte"] / d["launches"], 4),
-                         "mfma_frac": round(d["gflop"] / d["ms"] / peak, 5),
-                         "how": "the device kernel with the largest summed launch time in a profiled forward (HIP events on the launch stream around "
-                                "every launch, median of three forwards); achieved = its algorithmic flops or bytes / that time, whichever roof is nearer",
-                         "whole_forward_tflops": round(whole, 2), "whole_forward_frac": round(whole / peak, 5)},
-            "timing": {"method": "value = the MEDIAN of the repetitions of the K-step timed region", "repetitions": len(reps), "timed_seconds": round(sum(reps), 3), "ms_per_step_min": round(srt[0] / args.steps * 1e3, 3),
+            "timing": {"method": "value = the K-step timed region (with --min-seconds: the MEDIAN of its repetitions)", "repetitions": len(reps), "timed_seconds": round(sum(reps), 3), "ms_per_step_min": round(srt[0] / args.steps * 1e3, 3),
                        "ms_per_step_max": round(srt[-1] / args.steps * 1e3, 3)},
-            "self_check": check,
             "pipelining": {"forwards_in_flight": nfl,
                            "what": "consecutive steps rotate over %d launch plans (own workspace and output slab each, shared weights) on %d streams: the tail "
                                    "of step i overlaps the head of the next ones; every step is one whole batch-%d forward, all K steps finish inside "
                                    "the timed region" % (nfl, nfl, B) if nfl > 1 else "one forward at a time",
                            "one_forward_in_flight": serial},
-            "kernel_classes": classes,
-            "kernels": dict(sorted(kern.items(), key=lambda kv: -kv[1]["ms"])[:12]),
-            # the same launches grouped by the device kernel that ran them (per block shape = per template instantiation)
-            "by_symbol": dict(sorted(sym.items(), key=lambda kv: -kv[1]["ms"])[:10]),
         }
-        default_run = (B, args.hidden_dim_ratio, args.load_size, args.variant, args.dtype) == (8, 4, 256, "v3", "fp16")
-        if world == 1 and default_run and not args.no_extra_configs:
-            # the optional legs, each a fresh process of this file (run_child): a failing or hanging leg cannot cost the headline line, and a leg runs with the
-            # stream / hardware-queue state of a stand-alone run.  This process keeps its weights and workspaces meanwhile (20 GB of 288).
-            extra = {}
-            # what the sharded run's communication queue costs a rank, measured instead of modelled: the N = 1 code path WITH the gatherer (a world-1 RCCL
-            # communicator, 3 forward lanes, the wire conversion and an asynchronous all_gather_into_tensor behind every step: exactly the per-rank configuration
-            # of --gpus N) against the same 3 lanes without it, same box, back to back
-            if graphs is not None and nfl >= 3:
-                common = ["--steps", args.steps, "--warmup", args.warmup, "--min-seconds", min(0.4, args.min_seconds), "--in-flight", 3]
-                legs = {"three_lanes_no_gather": run_child(common), "three_lanes_with_gather": run_child(common + ["--force-gather"])}
-                if all("error" not in v for v in legs.values()):
-                    legs["ms_per_step_added_by_the_gather_queue"] = round(legs["three_lanes_with_gather"]["ms_per_step"] - legs["three_lanes_no_gather"]["ms_per_step"], 3)
-                    legs["gathered_equals_slab"] = legs["three_lanes_with_gather"].get("gathered_equals_slab")
-                legs["what"] = ("per-rank configuration of the sharded run on ONE GPU: 3 forwards in flight, each followed on its own lane by the wire conversion and an "
-                                "asynchronous RCCL all_gather_into_tensor of the %s output slab (world-1 communicator, torch's internal collective stream is the "
-                                "fourth busy queue), one gather slot per slab" % gdt)
-                extra["gather_overhead_1gpu"] = legs
-            # BASELINE configs 4 and 5, and the exact-fp32 path (the one that meets north_star's 1e-3 max-abs criterion) at the headline batch, so that their
-            # numbers are observed by whoever runs bench.py.  40 / 20-step regions: with 4 forwards in flight the fill and drain of a region is about one forward
-            for key, eargs in (("config4_batch4_1024x1024", ["--batch", 4, "--load-size", 512, "--steps", 20]),
-                               ("config5_batch16_hdr2", ["--batch", 16, "--hidden-dim-ratio", 2, "--steps", 40]),
-                               ("fp32_batch8", ["--dtype", "fp32", "--steps", 8])):
-                extra[key] = run_child(eargs + ["--warmup", 3, "--min-seconds", 0.4, "--in-flight", nfl])
-            result["extra_configs"] = extra
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
+        if args.full:
+            # per-kernel-class timing with HIP events on the launch stream (3 profiled forwards, median of sums)
+            profs = [net.profile(x) for _ in range(3)]
+            classes = {}
+            for name in net.KERNEL_CLASSES:
+                runs = sorted(p[name][0] for p in profs)
+                classes[name] = {"ms": round(runs[1], 4), "launches": profs[0][name][2], "gflop": round(profs[0][name][1] / 1e9, 2)}
+            peak = MFMA_PEAK_TFLOPS[args.dtype]
+            for c in classes.values():
+                c["tflops"] = round(c["gflop"] / c["ms"], 2) if c["ms"] > 0 and c["gflop"] > 0 else None
+            # per-KERNEL table from the per-launch records of the median profile: the roofline line names the dominant kernel
+            kern = {}
+            mid = sorted(profs, key=lambda p: sum(p[n][0] for n in net.KERNEL_CLASSES))[1]
+            for label, cls, fl, ms, _kn, _by in mid["launches"]:
+                k = kern.setdefault(kernel_key(label, cls), {"ms": 0.0, "gflop": 0.0, "launches": 0})
+                k["ms"] += ms; k["gflop"] += fl / 1e9; k["launches"] += 1
+            for k in kern.values():
+                k["ms"] = round(k["ms"], 4); k["gflop"] = round(k["gflop"], 2)
+                k["tflops"] = round(k["gflop"] / k["ms"], 1) if k["gflop"] > 0 and k["ms"] > 0 else None
+            # the same launches grouped by the DEVICE KERNEL that ran them (the template instantiation cfen_net_profile recorded at the launch site:
+            # every k_gemm_dma<T, 1, 3> launch of the forward is ONE entry, whatever block, level or step it served)
+            sym = {}
+            for label, cls, fl, ms, kname, nbytes in mid["launches"]:
+                k = sym.setdefault(kname, {"ms": 0.0, "gflop": 0.0, "gbyte": 0.0, "launches": 0})
+                k["ms"] += ms; k["gflop"] += fl / 1e9; k["gbyte"] += nbytes / 1e9; k["launches"] += 1
+            for k in sym.values():
+                k["ms"] = round(k["ms"], 4); k["gflop"] = round(k["gflop"], 2); k["gbyte"] = round(k["gbyte"], 4)
+                k["bound"], k["achieved"], _, k["unit"], k["frac"] = nearer_roof(k["gflop"], k["gbyte"], k["ms"], peak)
+            dom = max(sym, key=lambda k: sym[k]["ms"])                   # the device kernel the forward spends most time in
+            d = sym[dom]
+            bound, ach, rpeak, runit, rfrac = nearer_roof(d["gflop"], d["gbyte"], d["ms"], peak)
+            dom_launch_ms = d["ms"] / d["launches"]
+            whole = ips / world * flops_img / 1e12
+            from cfen_vit_dehazing_amd.parallel import split_slab
+            check = self_check(net, x, split_slab(slabs[(args.steps - 1) % nslab], B, n), cfg, args.dtype)   # what the last timed step wrote
+            if gather is not None:
+                # the GATHERED buffer of the last timed step, rank by rank: segment r must be rank r's images (synthetic_input seeds r * B ...), so its
+                # first image is checked against a batch-1 eager forward of that image computed here -- an ordering bug of the all-gather /
+                # merge_gathered on real RCCL shows up in the scaling run itself (reference analogue: nn.DataParallel's gather, v3:77-83)
+                from cfen_vit_dehazing_amd.parallel import merge_gathered
+                torch.cuda.synchronize()
+                merged = merge_gathered(gather.bufs[(args.steps - 1) % nslab].float(), world, B, n)
+                per_rank = []
+                for r in range(world):
+                    xi = synthetic_input(1, cfg, seed0=r * B).to(dev)
+                    one = net(xi)
+                    per_rank.append(round(max(float((m[r * B:r * B + 1] - o).abs().max()) for m, o in zip(merged, one)), 6))
+                check["gathered_image0_of_rank_vs_batch1_eager"] = per_rank
+                check["ok"] = check["ok"] and all(v <= check["bar"] for v in per_rank)
+            result["roofline"] = {"bound": bound, "kernel": dom, "achieved": ach, "peak": rpeak, "unit": runit, "frac": rfrac,
+                                   "traffic": None,
+                                   "traffic_from_profiles": pmc_traffic(dom),
+                                   "traffic_source": "`traffic` is not measured in this run (null); traffic_from_profiles = HBM bytes per launch of this kernel in the "
+                                                     "newest committed profiles/r*_pmc_traffic.json (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                                     "command, fetch x2 per the gfx950 guide)",
+                                   "launch_ms": round(dom_launch_ms, 4), "launches_per_step": d["launches"],
+                                   "algorithmic_gflop_per_launch": round(d["gflop"] / d["launches"], 2),
+                                   "algorithmic_gbyte_per_launch": round(d["gbyte"] / d["launches"], 4),
+                                   "mfma_frac": round(d["gflop"] / d["ms"] / peak, 5),
+                                   "how": "the device kernel with the largest summed launch time in a profiled forward (HIP events on the launch stream around "
+                                          "every launch, median of three forwards); achieved = its algorithmic flops or bytes / that time, whichever roof is nearer",
+                                   "whole_forward_tflops": round(whole, 2), "whole_forward_frac": round(whole / peak, 5)}
+            result["self_check"] = check
+            result["kernel_classes"] = classes
+            result["kernels"] = dict(sorted(kern.items(), key=lambda kv: -kv[1]["ms"])[:12])
+            # the same launches grouped by the device kernel that ran them (per block shape = per template instantiation)
+            result["by_symbol"] = dict(sorted(sym.items(), key=lambda kv: -kv[1]["ms"])[:10])
+            default_run = (B, args.hidden_dim_ratio, args.load_size, args.variant, args.dtype) == (8, 4, 256, "v3", "fp16")
+            if world == 1 and default_run and not args.no_extra_configs:
+                # the optional legs, each a fresh process of this file (run_child): a failing or hanging leg cannot cost the headline line, and a leg runs with the
+                # stream / hardware-queue state of a stand-alone run.  This process keeps its weights and workspaces meanwhile (20 GB of 288).
+                extra = {}
+                # what the sharded run's communication queue costs a rank, measured instead of modelled: the N = 1 code path WITH the gatherer (a world-1 RCCL
+                # communicator, 3 forward lanes, the wire conversion and an asynchronous all_gather_into_tensor behind every step: exactly the per-rank configuration
+                # of --gpus N) against the same 3 lanes without it, same box, back to back
+                if graphs is not None and nfl >= 3:
+                    common = ["--steps", args.steps, "--warmup", args.warmup, "--min-seconds", leg_seconds, "--in-flight", 3]
+                    legs = {"three_lanes_no_gather": run_child(common), "three_lanes_with_gather": run_child(common + ["--force-gather"])}
+                    if all("error" not in v for v in legs.values()):
+                        legs["ms_per_step_added_by_the_gather_queue"] = round(legs["three_lanes_with_gather"]["ms_per_step"] - legs["three_lanes_no_gather"]["ms_per_step"], 3)
+                        legs["gathered_equals_slab"] = legs["three_lanes_with_gather"].get("gathered_equals_slab")
+                    legs["what"] = ("per-rank configuration of the sharded run on ONE GPU: 3 forwards in flight, each followed on its own lane by the wire conversion and an "
+                                    "asynchronous RCCL all_gather_into_tensor of the %s output slab (world-1 communicator, torch's internal collective stream is the "
+                                    "fourth busy queue), one gather slot per slab" % gdt)
+                    extra["gather_overhead_1gpu"] = legs
+                # BASELINE configs 4 and 5, and the exact-fp32 path (the one that meets north_star's 1e-3 max-abs criterion) at the headline batch, so that their
+                # numbers are observed by whoever runs bench.py.  40 / 20-step regions: with 4 forwards in flight the fill and drain of a region is about one forward
+                for key, eargs in (("config4_batch4_1024x1024", ["--batch", 4, "--load-size", 512, "--steps", 20]),
+                                   ("config5_batch16_hdr2", ["--batch", 16, "--hidden-dim-ratio", 2, "--steps", 40]),
+                                   ("fp32_batch8", ["--dtype", "fp32", "--steps", 8])):
+                    extra[key] = run_child(eargs + ["--warmup", 3, "--min-seconds", 0.4, "--in-flight", nfl])
+                result["extra_configs"] = extra
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(result) + "\n").encode())
     if dist is not None:

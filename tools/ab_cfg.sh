@@ -12,7 +12,7 @@ for c in $cfgs; do
   esac
   for t in "$@"; do
     tt=$t; [ "$t" = "-" ] && tt=""
-    r=$(CFEN_TUNE="$tt" timeout 600 python3 bench.py $A --no-cpu-baseline --no-extra-configs --min-seconds ${MINSEC:-0.6} --steps 60 --in-flight ${INFLIGHT:-4} 2>/dev/null | python3 -c "
+    r=$(CFEN_TUNE="$tt" timeout 600 python3 bench.py $A --full --no-cpu-baseline --no-extra-configs --min-seconds ${MINSEC:-0.6} --steps 60 --in-flight ${INFLIGHT:-4} 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # The other BASELINE configurations and the sibling generators on the same code (informational; the headline is `python bench.py`):
 #   tools/bench_configs.sh <outfile>
 out=$1; : > $out
-run() { echo "== $*" >> $out; timeout -k 10 600 python3 bench.py --no-cpu-baseline --min-seconds 0.6 --steps 30 "$@" 2>/dev/null | python3 -c "
+run() { echo "== $*" >> $out; timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --min-seconds 0.6 --steps 30 "$@" 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
