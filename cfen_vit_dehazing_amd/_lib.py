@@ -99,6 +99,8 @@ SIGNATURES = {
     "cfen_embed_gather": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P]),
     "cfen_u8hwc_to_nhwc": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
     "cfen_tensor2im_u8": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cfen_tile_gather": (_I, [_I, _P, _P] + [_I] * 7 + [_P]),
+    "cfen_tile_blend": (_I, [_I, _P] + [_I] * 8 + [_P, _P, _P, _P]),
     "cfen_embed_qkv": (_I, [_I, ctypes.POINTER(EmbedQkvArgsC), _P]),
     "cfen_embed_qkv_stream": (_I, [_I, ctypes.POINTER(EmbedQkvArgsC), _P]),
     "cfen_layernorm": (_I, [_I, _P, _P, _P, _P, _I, _I, c_float, _P]),

@@ -289,6 +289,13 @@ int cfen_u8hwc_to_nhwc(int dtype, const unsigned char* in, void* out, int B, int
 int cfen_tensor2im_u8(const float* in, unsigned char* out, int C, int H, int W, void* stream) {
   return cfen_tensor2im_u8_impl(in, out, C, H, W, (hipStream_t)stream);
 }
+int cfen_tile_gather(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, void* stream) {
+  return cfen_tile_gather_impl(u8, src, dst, H, W, T, ny, nx, t0, B, (hipStream_t)stream);
+}
+int cfen_tile_blend(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs, void* xd,
+                    void* stream) {
+  return cfen_tile_blend_impl(dtype, arena, B, T, H, W, ny, nx, overlap, out_u8, xr, xs, xd, (hipStream_t)stream);
+}
 
 int cfen_tune(const char* key, int value) {
   CFEN_CHECK_ARG(key != nullptr, "tune: null key");

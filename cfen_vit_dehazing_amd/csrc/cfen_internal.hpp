@@ -68,6 +68,10 @@ int cfen_patchify_impl(int dtype, const void* fmap, void* tok, int B, int H, int
 int cfen_upsample4_impl(int dtype, const void* small, void* out, int B, int h, int w, int C, int cs_in, int cs_out, hipStream_t s);
 int cfen_nchw_to_nhwc_impl(int dtype, const float* in, void* out, int B, int C, int H, int W, int cs, hipStream_t s);
 int cfen_tensor2im_u8_impl(const float* in, unsigned char* out, int C, int H, int W, hipStream_t s);
+// overlapping-tile inference (k_tile.hip)
+int cfen_tile_gather_impl(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, hipStream_t s);
+int cfen_tile_blend_impl(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs,
+                         void* xd, hipStream_t s);
 int cfen_u8hwc_to_nhwc_impl(int dtype, const unsigned char* in, void* out, int B, int H, int W, int cs, hipStream_t s);
 int cfen_conv_impl(int dtype, const ConvDesc* d, hipStream_t s);
 // LDS-tiled stride-1 path (k_conv_tile.hip); weights in the "rows" layout, d->Kpad == cfen_conv_tile_kpad

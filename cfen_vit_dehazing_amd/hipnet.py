@@ -415,6 +415,13 @@ class dec_ipt(nn.Module):
             return [torch.stack([ops.tensor2im_u8(t[b].contiguous()) for b in range(B)]) for t in (xr, xs, xd)]
         return [xr, xs, xd]
 
+    def forward_tiled(self, image, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=None):
+        """[xr, xs, xd] of ONE image of any size, run as overlapping image_size x image_size tiles (tiled.dehaze_tiled); forward() itself keeps
+        refusing anything but the baked-in size"""
+        from . import tiled
+        kw = {} if max_arena_bytes is None else {"max_arena_bytes": max_arena_bytes}
+        return tiled.dehaze_tiled(self, image, overlap=overlap, tile_batch=tile_batch, output_u8=output_u8, **kw)
+
     def set_scale(self, scale_idx):
         self.scale_idx = scale_idx
 

@@ -79,6 +79,11 @@ class DECHLGVIT(BaseModel):
         # test.py only turns the outputs into PNGs (util.tensor2im, util/util.py:12-24): the generator writes those bytes itself -- (B,H,W,3) uint8
         # from the tails' last launch where the geometry allows, a device pass elsewhere (hipnet.dec_ipt.output_u8) -- instead of fp32 planes
         self._u8_out = not getattr(opt, 'isTrain', False) and getattr(opt, 'phase', 'test') == 'test' and hasattr(self.netG, 'output_u8')
+        # --tile: every image runs as overlapping image_size x image_size tiles (tiled.py, any input size); the fp32 comparison above is not extended to them
+        self._tile = bool(getattr(opt, 'tile', False))
+        if self._tile and self._half_guard:
+            print('notice: --precision half with --tile: the fp32 guard does not cover tiled images; they run in fp16 unchecked')
+            self._half_guard = False
 
     def _guard_dir(self):
         import os
@@ -181,6 +186,17 @@ class DECHLGVIT(BaseModel):
         if not self.actnorm_ready():
             return False           # the first REAL batch must initialise those layers (models/actnorm.py:25-37), not a dummy
         n = self.netG.cfg.image_size
+        if getattr(self, '_tile', False):
+            # the tiled path runs batches of up to --tile_batch tiles with float outputs (tiled.py): build that plan
+            batch_size = max(1, int(getattr(self.opt, 'tile_batch', 8)))
+            x = torch.zeros((batch_size, n, n, 3) if u8_input else (batch_size, 3, n, n), dtype=torch.uint8 if u8_input else torch.float32, device=self.device)
+            keep = self.netG.output_u8
+            self.netG.output_u8 = False
+            with torch.no_grad():
+                self.netG(x)
+            self.netG.output_u8 = keep
+            torch.cuda.synchronize()
+            return True
         shape = (batch_size, n, n, 3) if u8_input else (batch_size, 3, n, n)
         x = self._staged(torch.zeros(shape, dtype=torch.uint8 if u8_input else torch.float32)).to(self.device)
         with torch.no_grad():
@@ -215,6 +231,11 @@ class DECHLGVIT(BaseModel):
     def forward(self):
         j = self._batch_index
         self._batch_index = j + 1
+        if getattr(self, '_tile', False):
+            o = self.opt
+            [self.fake_R, self.fake_S, self.fake_A] = self.netG.forward_tiled(self._net_in, overlap=getattr(o, 'tile_overlap', None),
+                                                                             tile_batch=getattr(o, 'tile_batch', 8), output_u8=getattr(self, '_u8_out', False))
+            return
         if self.guard_due(j):
             self.netG.output_u8 = False                   # the guard compares the float outputs
             self.netG.set_compute_dtype('fp32')

@@ -347,6 +347,41 @@ def tensor2im_u8(x):
     return out
 
 
+def tile_gather(img, T, ny, nx, t0, B, out=None):
+    """cfen_tile_gather: tiles [t0, t0 + B) of the ny x nx tile plan (tiled.tile_grid) of `img` -- (H,W,3) uint8 or (3,H,W) fp32 CUDA tensor -- into
+    the network's input slab: (B,T,T,3) uint8 or (B,3,T,T) fp32 (`out`, else allocated).  Tile indices past ny*nx repeat the last tile."""
+    _cuda(img, out)
+    u8 = img.dtype == torch.uint8
+    if img.dim() != 3 or (u8 and img.shape[2] != 3) or (not u8 and (img.dtype != torch.float32 or img.shape[0] != 3)):
+        raise ValueError("tile_gather needs a contiguous (H,W,3) uint8 or (3,H,W) float32 image, got %s %s" % (tuple(img.shape), img.dtype))
+    H, W = (img.shape[0], img.shape[1]) if u8 else (img.shape[1], img.shape[2])
+    shape = (B, T, T, 3) if u8 else (B, 3, T, T)
+    if out is None:
+        out = torch.empty(shape, dtype=img.dtype, device=img.device)
+    elif tuple(out.shape) != shape or out.dtype != img.dtype:
+        raise ValueError("tile_gather: out must be a %s tensor of shape %s" % (img.dtype, shape))
+    check(_lib.load().cfen_tile_gather(int(u8), ptr(img), ptr(out), H, W, T, ny, nx, t0, B, current_stream()), "tile_gather")
+    return out
+
+
+def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False):
+    """cfen_tile_blend: the tile outputs in `arena` -- the forwards' [xr | xs | xd] output slabs of B tiles each, back to back, float32 or float16 --
+    blended into the H x W image: [xr (3,H,W), xs (1,H,W), xd (3,H,W)] float32, or with output_u8 three (H,W,3) uint8 images (util.tensor2im's bytes)"""
+    _cuda(arena)
+    need = -(-(ny * nx) // B) * 7 * B * T * T
+    if arena.dtype not in (torch.float32, torch.float16) or arena.numel() < need:
+        raise ValueError("tile_blend: the arena must hold %d float32 / float16 elements (%d slabs of 7*%d*%d*%d), got %d %s"
+                         % (need, need // (7 * B * T * T), B, T, T, arena.numel(), arena.dtype))
+    dev = arena.device
+    if output_u8:
+        outs = [torch.empty(H, W, 3, dtype=torch.uint8, device=dev) for _ in range(3)]
+    else:
+        outs = [torch.empty(c, H, W, dtype=torch.float32, device=dev) for c in (3, 1, 3)]
+    check(_lib.load().cfen_tile_blend(dtype_code(arena.dtype), ptr(arena), B, T, H, W, ny, nx, overlap, int(output_u8), ptr(outs[0]), ptr(outs[1]),
+                                      ptr(outs[2]), current_stream()), "tile_blend")
+    return outs
+
+
 def u8hwc_to_nhwc(img, cs, dtype):
     """(B,H,W,3) uint8 CUDA tensor -> normalised NHWC [B,H,W,cs] of `dtype` (ToTensor + Normalize(0.5, 0.5) + layout)"""
     _cuda(img)

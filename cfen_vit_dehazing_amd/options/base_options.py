@@ -79,6 +79,11 @@ class BaseOptions():
         p.add_argument('--u8_input', action='store_true',
                        help='(extension) the dataset hands over uint8 HWC images and ToTensor + Normalize(0.5, 0.5) run on the device '
                             'inside the generator launch plan (12x fewer bytes over PCIe); results are identical')
+        p.add_argument('--tile', action='store_true',
+                       help='(extension) dehaze images of any size: overlapping image_size x image_size tiles through the fixed-size generator, blended '
+                            'back to the input size (cfen_vit_dehazing_amd/tiled.py); needs --batchSize 1 and --in_flight 1')
+        p.add_argument('--tile_overlap', type=int, default=None, help='(extension) --tile: overlap of neighbouring tiles in pixels (default image_size // 8)')
+        p.add_argument('--tile_batch', type=int, default=8, help='(extension) --tile: tiles per forward')
         p.add_argument('--patch_dim', type=int, default=2)
         p.add_argument('--num_heads', type=int, default=4)
         p.add_argument('--num_layers', type=int, default=1)
@@ -114,6 +119,12 @@ class BaseOptions():
             opt.gpu_ids = [local]
         if opt.in_flight < 1:
             raise ValueError('--in_flight must be >= 1')
+        if getattr(opt, 'tile', False):
+            if opt.batchSize != 1 or opt.in_flight != 1:
+                raise ValueError('--tile runs one image at a time through the sequential loop: it needs --batchSize 1 and --in_flight 1 '
+                                 '(got --batchSize %d --in_flight %d)' % (opt.batchSize, opt.in_flight))
+            if opt.tile_batch < 1:
+                raise ValueError('--tile_batch must be >= 1')
         if not -1 <= opt.png_compress_level <= 9:
             raise ValueError('--png_compress_level must be -1 (PIL default) or 0..9')
         from ..util import util as _util

@@ -290,6 +290,26 @@ int cfen_nchw_to_nhwc(int dtype, const float* in, void* out, int B, int C, int H
 int cfen_u8hwc_to_nhwc(int dtype, const unsigned char* in, void* out, int B, int H, int W, int cs, void* stream);
 int cfen_tensor2im_u8(const float* in, unsigned char* out, int C, int H, int W, void* stream);
 
+/* Overlapping-tile inference of images of any size (tiled.py).  The image size is baked into the generator (learned positional tables and
+ * F.fold(..., img_dim): v3:1125-1127, 1186, 1321), so an H x W image runs as T x T tiles, T = cfg.image_size, through the unchanged forward.
+ * Tile plan per axis of extent L with overlap o (0 <= o <= T/2): n = 1 if L <= T else 1 + ceil((L - T) / (T - o)) tiles at origins
+ * p_j = (j (L - T)) // (n - 1) (p_0 = 0 when n = 1), numbered row-major t = i nx + j.  Tile pixel (u, v) of tile (i, j) is source pixel
+ * (mirror(p_i + u, H), mirror(q_j + v, W)), mirror = numpy 'reflect' (edge pixel not repeated; only where L < T).
+ *
+ * gather: tiles [t0, t0 + B) into the network's input slab; tile indices >= ny nx repeat the last tile (a full last batch).  A pure copy.
+ *   u8 = 1: src (H,W,3) uint8 -> dst (B,T,T,3) uint8 (a cfen_net_set_input_u8 net's input);  u8 = 0: src (3,H,W) fp32 -> dst (B,3,T,T) fp32.
+ *   T % 16 == 0; dst 16-byte aligned; the grid must tile the image (L <= T: n = 1; else n >= 2 and n T >= L).                                      */
+int cfen_tile_gather(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, void* stream);
+/* blend: the tile outputs back into the H x W image.  arena = the forwards' own output slabs back to back, dtype 0 fp32 / 1 fp16 (output_f16 nets):
+ *   slab s holds tiles [s B, s B + B) as [xr (B,3,T,T) | xs (B,1,T,T) | xd (B,3,T,T)] (7 B T T elements), tile t in slab t / B, slot t % B;
+ *   ceil(ny nx / B) slabs.  ny / nx must be the plan's tile counts for this overlap.
+ * Per output pixel: the tile value unchanged where one tile covers it; else sum(w v) / sum(w) in fp32 over the covering tiles in increasing t,
+ *   w = w(u) w(v), w(u) = min(1, (min(u, e - 1 - u) + 1) / (o + 1)), e = min(T, L).  No atomics: bitwise reproducible.
+ * out_u8 = 0: xr (3,H,W), xs (1,H,W), xd (3,H,W) fp32.  out_u8 = 1: xr / xs / xd each (H,W,3) uint8, tensor2im's arithmetic of the fp32 value
+ *   ((x+1)/2*255 truncated, xs tiled to 3 channels; util/util.py:12-24).  Outputs 16-byte aligned.                                                */
+int cfen_tile_blend(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs, void* xd,
+                    void* stream);
+
 /* Conv2d / ConvTranspose2d(4,2,1) as implicit GEMM with fused affine + activation + residuals.
  * kind 0: Conv2d(k, stride, pad) over nsrc (1..3) channel-concatenated inputs (src0 | src1 | src2, the concat is never
  * materialised: v3:488 torch.cat((local, global), 1); crs_gd4:854 cat of three); kind 1: ConvTranspose2d k4 s2 p1.
