@@ -398,6 +398,10 @@ int cfen_net::build() {
     v.ln_fold1 = !v.fused_front && v.Dn == v.D && (v.D * esz) % 128 == 0;
     v.ln_fold2 = !v.fused_mlp && v.Dn == v.D && (v.D * esz) % 128 == 0;
     CFEN_CHECK_ARG(v.Dn % v.heads == 0, "net: %s embedding dim %d not divisible by %d heads", v.name.c_str(), v.Dn, v.heads);
+    // the attention kernels' limits (dispatch_attn, k_attention.hip), refused here rather than at the first launch that meets them
+    CFEN_CHECK_ARG(v.dh % (16 / esz) == 0 && v.dh <= 128,
+                   "net: --num_heads %d gives %s a head dim of %d (embedding dim %d / %d heads); the %s attention kernels take head dims that are "
+                   "multiples of %d up to 128", cfg.num_heads, v.name.c_str(), v.dh, v.Da, v.heads, esz == 2 ? "fp16" : "fp32", 16 / esz);
     CFEN_CHECK_ARG(v.mapH % v.ws == 0 && v.ws % v.p == 0 && v.S >= 1, "net: %s does not tile its map", v.name.c_str());
     const size_t ntok = (size_t)B * (v.mapH / v.ws) * (v.mapH / v.ws) * v.S;
     (v.global ? max_md_g : max_md_l) = std::max(v.global ? max_md_g : max_md_l, ntok * std::max(v.D, v.Da));

@@ -100,6 +100,31 @@ class dec_ipt(nn.Module):
         # GViT block run as two persistent chains (csrc/k_gvit.hip) instead of eight launches; fp16 only.  OFF by default: measured slower inside the
         # forward (3.15 against 2.80 ms at B = 8, round 4: grid barriers, split-K seams and write-through stores cost more than the launches they replace)
         self.gvit_chain = os.environ.get("CFEN_GVIT_CHAIN", "0") != "0"
+        self._check_plan()
+
+    def _config_c(self, batch, dtype):
+        c = self.cfg
+        return NetConfigC(batch=batch, n_feats=c.n_feats, hidden_dim_ratio=c.hidden_dim_ratio, patch_size=c.patch_size,
+                          load_size=c.load_size, num_heads=c.num_heads, dtype=_lib.dtype_code(dtype),
+                          reserved=(1 if self.serial_plan else 0) | (2 if self.wtile else 0) | (4 if self.gvit_chain else 0) | (_VARIANT_CODE[c.variant] << 8))
+
+    def _check_plan(self, dtype=None):
+        """Refuse, before any weights move or any kernel launches, a configuration the kernels cannot run.  Host-side mirror of cfen_net::build's
+        checks (csrc/cfen_net.cpp), which refuse the same at cfen_net_create; kept in Python so that building the module does not call into the
+        HIP library before the caller has touched the device."""
+        c, dtype = self.cfg, _DTYPES[dtype or self.compute_dtype]
+        if 4 * c.n_feats > 128:
+            raise CfenError("--n_feats %d is not supported: the token kernels take n_feats <= 32" % c.n_feats)
+        if c.hidden_dim_ratio <= 0 or c.num_heads <= 0 or (4 * c.n_feats) % c.num_heads:
+            raise CfenError("--hidden_dim_ratio %d / --num_heads %d: the ratio must be positive and the heads must divide 4 * n_feats"
+                            % (c.hidden_dim_ratio, c.num_heads))
+        epl = 8 if dtype == torch.float16 else 4              # elements per 16-byte MFMA fragment row (csrc/cfen_common.hpp Mma<T>::EPL)
+        for v in c.vit_instances():
+            dh = -(-v.dim // v.heads // 8) * 8 if v.shrink > 1 else v.dim // v.heads      # v5: head dim padded to 8 (cfen_net::build)
+            if dh % epl or dh > 128:
+                raise CfenError("--num_heads %d gives %s a head dim of %d (embedding dim %d / %d heads); the %s attention kernels take head dims "
+                                "that are multiples of %d up to 128" % (c.num_heads, v.name, dh, v.dim, v.heads,
+                                                                        "fp16" if dtype == torch.float16 else "fp32", epl))
 
     # ---- parameter management ---------------------------------------------------------------
     def state_dict(self, *args, **kw):
@@ -188,6 +213,7 @@ class dec_ipt(nn.Module):
         dtype = _DTYPES[dtype]
         if dtype == self.compute_dtype:
             return
+        self._check_plan(dtype)
         if self._packed is not None and not self._an_pending:
             # (a packed set whose ActNorm layers are still uninitialised is NOT kept: once they are initialised under the other type its epilogue tables and its
             # pending list would be stale -- the next forward of this type would initialise ActNorm again, from another batch; it is repacked instead.  ADVICE r05)
@@ -249,10 +275,7 @@ class dec_ipt(nn.Module):
                                 "(ops.tune('gvit.max_concurrent', n) BEFORE building the nets caps the teams accordingly)"
                                 % (self.replica, int(self.replica) + 1, allowed))
         lib = _lib.load()
-        c = self.cfg
-        cc = NetConfigC(batch=batch, n_feats=c.n_feats, hidden_dim_ratio=c.hidden_dim_ratio, patch_size=c.patch_size,
-                        load_size=c.load_size, num_heads=c.num_heads, dtype=_lib.dtype_code(self.compute_dtype),
-                        reserved=(1 if self.serial_plan else 0) | (2 if self.wtile else 0) | (4 if self.gvit_chain else 0) | (_VARIANT_CODE[c.variant] << 8))
+        cc = self._config_c(batch, self.compute_dtype)
         # bit 0: single-stream plan; bit 1: tile-major GViT weights; bit 2: GViT fragment streams (persistent chains); bits 8..15: variant
         h = ctypes.c_void_p()
         check(lib.cfen_net_create(ctypes.byref(h), ctypes.byref(cc)), "cfen_net_create")

@@ -14,7 +14,8 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def load_net_fixture(name):
     z = np.load(os.path.join(GOLDEN, "net_%s.npz" % name))
     nf, hdr, ps, ls = [int(v) for v in z["cfg"]]
-    cfg = NetConfig(nf, hdr, patch_size=ps, load_size=ls, variant=variant_of(name))
+    heads = int(z["num_heads"]) if "num_heads" in z else 4        # the older fixtures were all made at the reference default of 4
+    cfg = NetConfig(nf, hdr, patch_size=ps, load_size=ls, num_heads=heads, variant=variant_of(name))
     return cfg, int(z["batch"]), z
 
 

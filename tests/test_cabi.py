@@ -110,3 +110,51 @@ def test_packed_parameters_match_the_plan_where_the_fused_kernels_do_not_apply(n
     embedding dims whose rows are not whole 128-byte K steps (n_feats 8: D = 32, 128), and the D = 384 fragment-stream blocks"""
     from cfen_vit_dehazing_amd.config import NetConfig
     _pack_and_register(NetConfig(n_feats, hdr, patch_size=patch, load_size=8 * patch), dtype, True)
+
+
+@pytest.mark.parametrize("n_feats,num_heads,dtype,flag", [(40, 4, "fp16", b"n_feats"), (40, 4, "fp32", b"n_feats"),
+                                                          (24, 8, "fp16", b"--num_heads 8"), (16, 16, "fp16", b"--num_heads 16"),
+                                                          (32, 2, "fp16", b"--num_heads 2"), (32, 2, "fp32", b"--num_heads 2")])
+def test_configurations_the_kernels_cannot_run_are_refused_at_create(n_feats, num_heads, dtype, flag):
+    """refused by cfen_net_create (host-side plan build, no launch), with a message that names the flag: n_feats 40 (token rows over 128
+    elements), head dims the attention kernels do not take -- 12 (n_feats 24, 8 heads) and 4 (n_feats 16, 16 heads) are not multiples of the
+    fp16 fragment width of 8, GViT-1 of n_feats 32 at 2 heads has a head dim of 256 > 128"""
+    import torch
+    from cfen_vit_dehazing_amd import _lib
+    lib = _lib.load()
+    cc = _lib.NetConfigC(batch=1, n_feats=n_feats, hidden_dim_ratio=4, patch_size=8, load_size=64, num_heads=num_heads,
+                         dtype=_lib.dtype_code(torch.float16 if dtype == "fp16" else torch.float32), reserved=0)
+    h = ctypes.c_void_p()
+    assert lib.cfen_net_create(ctypes.byref(h), ctypes.byref(cc)) == -1
+    assert flag in lib.cfen_last_error(), lib.cfen_last_error()
+
+
+@pytest.mark.parametrize("n_feats,num_heads,dtype,flag", [(40, 4, "fp32", "n_feats"), (24, 8, "fp16", "--num_heads 8"), (16, 16, "fp16", "--num_heads 16"),
+                                                          (32, 2, "fp32", "--num_heads 2")])
+def test_dec_ipt_refuses_them_when_it_is_built(n_feats, num_heads, dtype, flag):
+    """dec_ipt(cfg, compute_dtype=...) checks the launch plan on construction, before any weights move to the device or any kernel launches"""
+    from cfen_vit_dehazing_amd._lib import CfenError
+    from cfen_vit_dehazing_amd.config import NetConfig
+    from cfen_vit_dehazing_amd.hipnet import dec_ipt
+    with pytest.raises(CfenError, match=flag):
+        dec_ipt(NetConfig(n_feats, 4, patch_size=8, load_size=64, num_heads=num_heads), compute_dtype=dtype)
+
+
+def test_switching_to_a_dtype_the_heads_do_not_fit_is_refused():
+    """n_feats 24 at 8 heads: LViT head dim 12 runs in fp32 (fragment width 4), not in fp16 (8); the switch is refused, the net stays fp32"""
+    import torch
+    from cfen_vit_dehazing_amd._lib import CfenError
+    from cfen_vit_dehazing_amd.config import NetConfig
+    from cfen_vit_dehazing_amd.hipnet import dec_ipt
+    net = dec_ipt(NetConfig(24, 4, patch_size=8, load_size=64, num_heads=8), compute_dtype="fp32")
+    with pytest.raises(CfenError, match="--num_heads 8"):
+        net.set_compute_dtype("fp16")
+    assert net.compute_dtype == torch.float32
+
+
+@pytest.mark.parametrize("n_feats,hdr,num_heads,dtype", [(32, 6, 4, "fp16"), (32, 6, 4, "fp32"), (32, 6, 8, "fp16"), (16, 3, 4, "fp16"),
+                                                         (8, 4, 4, "fp16"), (8, 1, 4, "fp32"), (16, 4, 16, "fp32")])
+def test_configurations_the_kernels_run_are_accepted(n_feats, hdr, num_heads, dtype):
+    from cfen_vit_dehazing_amd.config import NetConfig
+    from cfen_vit_dehazing_amd.hipnet import dec_ipt
+    dec_ipt(NetConfig(n_feats, hdr, patch_size=8, load_size=64, num_heads=num_heads), compute_dtype=dtype)

@@ -1079,3 +1079,108 @@ def test_half_guard_catches_an_overflow_that_starts_on_a_later_batch(tmp_path):
     assert torch.equal(batch3_fake_A, ref(synthetic_input(2, cfg, seed0=6).to("cuda:0"))[2])
     txt = open(tmp_path / "res" / "late_overflow" / "test_latest" / "precision.txt").read()
     assert "precision: single" in txt and "fell_back_at_batch: 3" in txt
+
+
+# ---- off n_feats 24: the CLI defaults (--n_feats 32 --hidden_dim_ratio 6), an odd ratio, n_feats 8 and 8 heads ------------------------
+# None of the fused fast paths apply there (packing.py gates them on D in {96, 192, 384}): these run the generic launches at LViT head dims
+# 32 / 16 / 8, GViT head dims 128 / 64 / 32, GViT-3 at D = 2048 with a 12288-wide hidden layer, and 64-byte fp16 token rows (n_feats 8)
+
+OFF_NF24 = ["tiny_nf32_hdr6", "tiny_nf16_hdr3", "tiny_nf8_hdr4", "tiny_nf32_hdr6_h8"]
+
+
+@pytest.mark.parametrize("name", OFF_NF24 + ["full512_nf32_hdr6"])
+def test_fp32_off_nf24_matches_reference_vectors_all_stages(name):
+    cfg, batch, z = load_net_fixture(name)
+    net = make_net(cfg, "fp32")
+    outs = net(synthetic_input(batch, cfg).to("cuda:0"))
+    st = gpu_stages(net, z)
+    for nm, o in zip(("tail_R", "tail_S", "tail_D"), outs):
+        st[nm] = o
+    worst = check_stages(z, st, 3e-4 if name.startswith("full512") else 2e-4, rel_sum=2e-4)
+    wo = check_outputs(z, outs, 1e-4)
+    print("%s fp32: worst stage sample diff %.2e, outputs %.2e" % (name, worst, wo))
+    del net
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("name", OFF_NF24 + ["full512_nf32_hdr6"])
+def test_fp16_off_nf24_psnr_ssim_against_oracle(name):
+    """dec_ipt(cfg, compute_dtype="fp16") directly (no half guard that could switch the run to fp32) against the oracle on the same weights;
+    full512_nf32_hdr6 (what test.py runs at its defaults on a 512 x 512 image) also against the reference's own samples"""
+    cfg, batch, z = load_net_fixture(name)
+    sd = generate_state_dict(cfg, seed=0, with_dead=False)
+    x = synthetic_input(batch, cfg)
+    with torch.no_grad():
+        ref = cfen_oracle.forward(sd, x, cfg.num_heads, cfg.patch_size)
+    net = make_net(cfg, "fp16")
+    assert net.compute_dtype == torch.float16
+    got = [o.float().cpu() for o in net(x.to("cuda:0"))]
+    for nm, (dp, ds, p, mx) in zip(("xr", "xs", "xd"), _psnr_ssim_delta(ref, got, x)):
+        print("%s fp16 %s: dPSNR %.4f dB, dSSIM %.2e, PSNR(fp16 vs ref) %.1f dB, max-abs %.2e" % (name, nm, dp, ds, p, mx))
+        assert dp <= 0.01 and ds <= 1e-4
+        assert p >= 50.0 and mx <= FP16_BAR
+    if name.startswith("full512"):
+        worst = check_outputs(z, got, FP16_BAR)
+        print("%s fp16 outputs max-abs vs reference vectors %.2e" % (name, worst))
+        for nm, o in zip(("xr", "xs", "xd"), got):
+            stat = z["stat/" + nm]
+            assert abs(float(o.mean()) - stat[0]) < 2e-3 and abs(float(o.std()) - stat[1]) < 2e-3
+    del net
+    torch.cuda.empty_cache()
+
+
+def test_graph_replay_equals_eager_at_the_cli_defaults():
+    """n_feats 32, hidden_dim_ratio 6, batch 2, fp16: the captured hipGraph replays the eager plan bit for bit, also on new input content"""
+    cfg, _, _ = load_net_fixture("tiny_nf32_hdr6")
+    net = make_net(cfg, "fp16")
+    x = synthetic_input(2, cfg).to("cuda:0")
+    eager = [o.clone() for o in net(x)]
+    gid, outs = net.capture(x)
+    for o in outs:
+        o.zero_()
+    net.replay(gid)
+    torch.cuda.synchronize()
+    for a, b in zip(eager, outs):
+        assert torch.equal(a, b)
+    x.copy_(synthetic_input(2, cfg, seed0=5).to("cuda:0"))
+    net.replay(gid)
+    want = [o.clone() for o in outs]
+    for a, b in zip(want, net(x)):
+        assert torch.equal(a, b)
+
+
+def test_cli_at_its_default_n_feats_and_hidden_dim_ratio(tmp_path):
+    """python test.py WITHOUT --n_feats / --hidden_dim_ratio runs the reference's defaults (32 / 6, options/base_options.py): PNGs within one
+    grey level of tensor2im(oracle output) on a synthetic n_feats 32 / hidden_dim_ratio 6 checkpoint"""
+    import os
+    import subprocess
+    import sys
+    from PIL import Image
+    from cfen_vit_dehazing_amd.util import util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cfg = NetConfig(32, 6, patch_size=8, load_size=64)
+    sd = generate_state_dict(cfg, seed=0)
+    name = "iid_hlgvit_crs_gd4_cfs_v3_defaults"
+    os.makedirs(tmp_path / "ckpt" / name)
+    torch.save(sd, tmp_path / "ckpt" / name / "32_net_G.pth")
+    os.makedirs(tmp_path / "data" / "hazy")
+    rs = np.random.RandomState(1)
+    imgs = []
+    for i in range(2):
+        a = rs.randint(0, 256, (128, 128, 3), dtype=np.uint8)
+        Image.fromarray(a).save(tmp_path / "data" / "hazy" / ("syn_%04d.png" % (i + 1)))
+        imgs.append(a)
+    cmd = [sys.executable, os.path.join(root, "test.py"), "--dataroot", str(tmp_path / "data"), "--name", name, "--sb", "--out_all",
+           "--which_epoch", "32", "--loadSize", "64", "--patch_size", "8", "--checkpoints_dir", str(tmp_path / "ckpt"),
+           "--results_dir", str(tmp_path / "res"), "--precision", "single"]
+    subprocess.check_call(cmd, cwd=str(tmp_path))
+    out_dir = tmp_path / "res" / name / "test_32" / "images"
+    assert sorted(os.listdir(out_dir)) == ["syn_%04d_fake_A.png" % (i + 1) for i in range(2)]
+    for i, a in enumerate(imgs):
+        x = (torch.from_numpy(a).permute(2, 0, 1).float() / 255 - 0.5) / 0.5
+        with torch.no_grad():
+            xd = cfen_oracle.forward(sd, x[None], cfg.num_heads, cfg.patch_size)[2]
+        want = util.tensor2im(xd[0]).astype(np.int32)
+        got = np.asarray(Image.open(out_dir / ("syn_%04d_fake_A.png" % (i + 1)))).astype(np.int32)
+        assert got.shape == want.shape and np.abs(got - want).max() <= 1
+        assert (got != want).mean() < 0.01

@@ -1062,3 +1062,198 @@ def test_head_conv5_from_the_network_input(u8, B, H, W):
     assert float(got[..., 12:].abs().max()) == 0.0
     relu = ops.head_conv5((img if u8 else x).to(d).contiguous(), w.to(d), bias.to(d), act=1)
     close(relu[..., :12], torch.relu(want), tol(torch.float16, 4), "with ReLU")
+
+
+# ---- the shapes the generator launches off n_feats 24 (n_feats 8 / 16 / 32, hidden_dim_ratio 3 / 4 / 6, num_heads 4 / 8) --------------
+# where none of the fused fast paths apply, so the generic kernels meet head dims 8 .. 128, GViT-3 at D = 2048 with a 12288-wide hidden
+# layer, fp16 token rows of 64 bytes (D = 32) and 4- / 8- / 16-channel conv maps.  Each case sits at the shape of a launch of
+# tests/test_hip_net.py's off-n_feats-24 configurations (the layer named in the comment).
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dh", [8, 16, 32, 64, 128])
+def test_attention_off_nf24_head_dims(dtype, dh):
+    """LViT head dims 8 (n_feats 8), 16 (n_feats 16; n_feats 32 at 8 heads), 32 (n_feats 32) over windows of 16 / 64 / 256 tokens; GViT head
+    dims 32 / 64 / 128 over 1 / 4 / 16 / 64 pooled tokens (GViT-3 .. GViT-1 at loadSize 64 and 256)"""
+    for S, heads, nseq in ((1, 16, 2), (4, 8, 2), (16, 4, 3), (64, 8, 2), (256, 4, 2)):
+        qkv = rnd((nseq * S, 3 * heads * dh), 7 + S, dtype, 1.5)
+        got = ops.attention(qkv.to(dev()), nseq, S, heads)
+        close(got, attn_ref(qkv, nseq, S, heads), tol(dtype, 3), "S %d heads %d dh %d" % (S, heads, dh))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,D", [(1024, 32), (512, 64), (16, 128), (256, 256), (4, 512), (8, 1024), (2, 2048)])
+def test_layernorm_off_nf24_widths(dtype, M, D):
+    """D = 32: 64-byte fp16 rows (LViT-1 of n_feats 8, k_layernorm with 16-lane row groups); the others: LViT / GViT widths of n_feats 8 .. 32"""
+    x = rnd((M, D), 1, dtype, 2.0) + 0.5
+    g, b = 1 + 0.1 * rnd((D,), 2, torch.float32), 0.1 * rnd((D,), 3, torch.float32)
+    want = cfen_oracle.layer_norm(x.double(), g.double(), b.double())
+    close(ops.layernorm(x.to(dev()), g.to(dev()), b.to(dev())), want, tol(dtype, 4))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,N,K", [(1024, 32, 32), (1024, 96, 32), (1024, 128, 32), (1024, 32, 128), (256, 64, 64), (256, 192, 64),
+                                   (256, 256, 64), (256, 64, 256), (100, 48, 32)])
+def test_gemm_short_k_rows(dtype, M, N, K):
+    """n_feats 8: the LViT token GEMMs of levels 1 and 2 (embed / qkv / ffn1 / ffn2 / proj at D = 32, 64) take k_gemm_nt's zero-filled K
+    tail in fp16 (K = 32 is one half of a 64-element K step); all epilogues against fp64"""
+    x, w = rnd((M, K), 1, dtype), rnd((N, K), 2, dtype, 1 / math.sqrt(K))
+    bias, res, pos = rnd((N,), 3, torch.float32), rnd((M, N), 4, dtype), rnd((16, N), 5, dtype)
+    ref = x.double() @ w.double().t()
+    d = dev()
+    close(ops.gemm_nt(x.to(d), w.to(d)), ref, tol(dtype, 4), "plain")
+    want = torch.relu(ref + bias.double()) + res.double() + pos.double()[torch.arange(M) % 16]
+    close(ops.gemm_nt(x.to(d), w.to(d), bias=bias.to(d), residual=res.to(d), pos=pos.to(d), relu=True), want, tol(dtype, 8), "epilogues")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,N,K", [(2, 6144, 2048), (16, 12288, 2048), (16, 2048, 12288), (128, 2048, 12288), (8, 2048, 2048), (128, 12288, 2048),
+                                   (64, 3072, 512), (4, 1024, 6144)])
+def test_gemm_widest_gvit_shapes(dtype, M, N, K):
+    """GViT-3 of n_feats 32 / hidden_dim_ratio 6 (D = 2048, hidden 12288): qkv, ffn1, ffn2, proj at B x 1 tokens (loadSize 64) and B x 16 tokens
+    (loadSize 256, B = 1 and 8) -- the widest K and N the GEMM dispatch sees -- and GViT-1 / GViT-2 shapes of the same configuration"""
+    x, w = rnd((M, K), 1, dtype), rnd((N, K), 2, dtype, 1 / math.sqrt(K))
+    bias, res = rnd((N,), 3, torch.float32), rnd((M, N), 4, dtype)
+    ref = x.double() @ w.double().t()
+    d = dev()
+    close(ops.gemm_nt(x.to(d), w.to(d)), ref, tol(dtype, 4), "plain")
+    close(ops.gemm_nt(x.to(d), w.to(d), bias=bias.to(d), residual=res.to(d), relu=True), torch.relu(ref + bias.double()) + res.double(),
+          tol(dtype, 8), "bias + relu + residual")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,D,N", [(16, 2048, 12288), (2, 2048, 6144), (128, 1024, 6144), (512, 64, 256), (256, 256, 768)])
+def test_gemm_ln_off_nf24(dtype, M, D, N):
+    """norm -> in_proj / linear1 folded into one GEMM (packing.ln_folded) at GViT-3 of n_feats 32 (D = 2048), GViT-2, and the LViT rows of
+    n_feats 8 (D = 64: one 128-byte fp16 step) and n_feats 16 / hidden_dim_ratio 3"""
+    from cfen_vit_dehazing_amd.packing import ln_folded
+    x = rnd((M, D), 1, dtype, 2.0) + 1.0
+    w = rnd((N, D), 2, torch.float32, D ** -0.5)
+    g, b, bias = 1 + 0.1 * rnd((D,), 3, torch.float32), 0.1 * rnd((D,), 4, torch.float32), rnd((N,), 5, torch.float32)
+    want = (cfen_oracle.layer_norm(x.double(), g.double(), b.double()) @ w.double().t() + bias.double()).relu()
+    f = ln_folded(None, g, b, bias, "l", dtype, w)
+    got = ops.gemm_ln(x.to(dev()), f["l.wl"].to(dev()), f["l.s"].to(dev()), f["l.bl"].to(dev()), relu=True)
+    close(got, want, tol(dtype, 8))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,N,K,nsplit", [(16, 2048, 12288, 8), (128, 2048, 12288, 4), (8, 2048, 2048, 2), (2, 12288, 2048, 2)])
+def test_gemm_split_k_widest_gvit_shapes(dtype, M, N, K, nsplit):
+    """split-K slices at GViT-3 of n_feats 32 / hidden_dim_ratio 6 (ffn2: K = 12288; proj; ffn1 at B = 2): fp64 reference, equal to the unsplit
+    GEMM within rounding, bit-reproducible, arrival counters back to zero"""
+    d = dev()
+    x, w = rnd((M, K), 1, dtype), rnd((N, K), 2, dtype, 1 / math.sqrt(K))
+    bias, res = rnd((N,), 3, torch.float32), rnd((M, N), 4, dtype)
+    tiles = ((N + 95) // 96) * ((M + 31) // 32)
+    scratch = torch.zeros(4096 + tiles * nsplit * 14336, dtype=torch.uint8, device=d)
+    want = torch.relu(x.double() @ w.double().t() + bias.double()) + res.double()
+    full = ops.gemm_splitk(x.to(d), w.to(d), nsplit, bias=bias.to(d), residual=res.to(d), relu=True, scratch=scratch)
+    close(full, want, tol(dtype, 6), "split")
+    assert int(scratch[:4096].view(torch.int32).abs().sum()) == 0
+    assert torch.equal(full, ops.gemm_splitk(x.to(d), w.to(d), nsplit, bias=bias.to(d), residual=res.to(d), relu=True, scratch=scratch))
+    close(full, ops.gemm_nt(x.to(d), w.to(d), bias=bias.to(d), residual=res.to(d), relu=True), tol(dtype, 6), "split vs unsplit")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cin,cout,k,stride,pad,size", [(4, 4, 3, 1, 1, 64), (4, 8, 3, 2, 1, 64), (8, 16, 3, 2, 1, 32), (8, 8, 3, 1, 1, 64),
+                                                       (16, 32, 3, 2, 1, 32), (32, 64, 3, 2, 1, 32), (64, 128, 3, 2, 1, 32),
+                                                       (4, 3, 7, 1, 3, 32), (8, 3, 3, 1, 1, 32)])
+def test_conv_off_nf24_widths(dtype, cin, cout, k, stride, pad, size):
+    """head ResBlock of n_feats 8 (4 channels), ds_conv_e01 .. e03 of n_feats 8 / 16 / 32 (4 -> 8 ... 64 -> 128), the tails' 3x3 / 7x7 on
+    4 / 8 channels"""
+    x = rnd((2, cin, size, size), 1, dtype)
+    w = rnd((cout, cin, k, k), 2, dtype, 1 / math.sqrt(cin * k * k))
+    b = rnd((cout,), 3, torch.float32, 0.1)
+    want = torch.relu(F.conv2d(x.double(), w.double(), b.double(), stride=stride, padding=pad))
+    close(run_conv(dtype, x, w, b, k, stride, pad, act=1), want, tol(dtype, 4))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cout", [4, 8])
+def test_conv_reflect7_tanh_on_few_channels(dtype, cout):
+    """tail_R / tail_D conv7 of n_feats 8 / 16: 4 or 8 input channels, reflect padding, tanh, fp32 NCHW out"""
+    x = rnd((2, cout, 32, 32), 1, dtype)
+    w = rnd((3, cout, 7, 7), 2, dtype, 0.3 / math.sqrt(cout * 49))
+    b = rnd((3,), 3, torch.float32, 0.1)
+    want = torch.tanh(F.conv2d(F.pad(x.double(), (3, 3, 3, 3), mode="reflect"), w.double(), b.double()))
+    got = run_conv(dtype, x, w, b, 7, 1, 3, reflect=True, act=2, nchw=True)
+    assert got.dtype == torch.float32 and got.shape == want.shape
+    close(got, want, tol(dtype, 2))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C", [8, 16, 32, 64, 128])
+def test_conv_1x1_concat_actnorm_relu_residual_off_nf24(dtype, C):
+    """lgcat_conv_e0l / d0l of n_feats 8 (C = 8 .. 32) and n_feats 32 (C = 32 .. 128); concat sources are whole multiples of 8 channels
+    (n_feats % 8 == 0), as packing.pack_conv_weight assumes"""
+    a, b2 = rnd((2, C, 16, 16), 1, dtype), rnd((2, C, 16, 16), 2, dtype)
+    w = rnd((C, 2 * C, 1, 1), 3, dtype, 1 / math.sqrt(2 * C))
+    bias, anw, anb = rnd((C,), 4, torch.float32, 0.1), rnd((C,), 5, torch.float32, 0.2), rnd((C,), 6, torch.float32, 0.2)
+    res = rnd((2, C, 16, 16), 7, dtype)
+    y = F.conv2d(torch.cat((a, b2), 1).double(), w.double(), bias.double())
+    want = torch.relu((y + anb.double().view(1, -1, 1, 1)) * torch.exp(anw.double()).view(1, -1, 1, 1)) + res.double()
+    close(run_conv(dtype, a, w, bias, 1, 1, 0, an=(anw, anb), act=1, res=res, x2=b2), want, tol(dtype, 6))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cin,cout", [(8, 4), (16, 8), (32, 16), (64, 32), (128, 64)])
+def test_conv_transpose_off_nf24_widths(dtype, cin, cout):
+    """us_conv_d0l of n_feats 8 / 16 / 32 (ConvTranspose2d 4x4 s2 p1 + ReLU); padded output channels stay zero"""
+    kc = 32 if dtype == torch.float16 else 16
+    d = dev()
+    x = rnd((2, cin, 16, 16), 1, dtype)
+    w = rnd((cin, cout, 4, 4), 2, dtype, 1 / math.sqrt(cin * 4))
+    b = rnd((cout,), 3, torch.float32, 0.1)
+    want = torch.relu(F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2, padding=1))
+    wp = packing.pack_convT_weight(w, packing.cs_of(cin), kc, dtype)
+    s, t = packing.affine(b, cout_pad=packing.round_up(cout, 16))
+    out = ops.conv2d(ops.to_nhwc(x).to(d), wp.to(d), s.to(d), t.to(d), packing.cs_of(cin), cout, transpose=True, act=1)
+    close(ops.from_nhwc(out, cout), want, tol(dtype, 4))
+    if packing.cs_of(cout) != cout:
+        assert float(out[..., cout:].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cout", [4, 8])
+def test_head_conv5_rows_layout_few_channels(dtype, cout):
+    """head.0.0 of n_feats 8 / 16: 3 -> 4 / 8 channels, 5x5 (k_conv_tile at 16 output channels)"""
+    x = rnd((2, 3, 16, 64), 1, dtype)
+    w = rnd((cout, 3, 5, 5), 2, dtype, 1 / math.sqrt(75))
+    b = rnd((cout,), 3, torch.float32, 0.1)
+    want = F.conv2d(x.double(), w.double(), b.double(), padding=2)
+    close(run_conv_rows(dtype, x, w, b, 5), want, tol(dtype, 4))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C", [8, 16, 32, 64, 128])
+def test_instnorm_relu_off_nf24_widths(dtype, C):
+    """ds_conv_e0l / us_conv_d03 InstanceNorm + ReLU on the channel counts of n_feats 8 .. 32 (n_feats .. 4 n_feats; the 4-channel maps of
+    n_feats 8 -- head and us_conv_d01 -- are not instance-normalised)"""
+    x = rnd((2, C, 16, 16), 1, dtype, 2.0) + 0.7
+    want = torch.relu(cfen_oracle.instance_norm(x.double()))
+    close(ops.from_nhwc(ops.instnorm_relu_(ops.to_nhwc(x).to(dev()), C), C), want, tol(dtype, 2))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C", [8, 16, 32, 64])
+def test_cfsm2g_off_nf24_widths(dtype, C):
+    """cfsm2g_d02d / d03d of n_feats 8 .. 32 (C = n_feats, 2 n_feats; the gates' hidden width C / 4) against the oracle in fp64"""
+    h = C // 4
+    g = torch.Generator().manual_seed(C)
+    sd = {}
+    for fc in ("fc_avg_cf1", "fc_avg_cf2", "fc_max_cf1", "fc_max_cf2"):
+        sd["c.%s.0.weight" % fc] = torch.randn(h, C, 1, 1, generator=g) / math.sqrt(C)
+        sd["c.%s.2.weight" % fc] = torch.randn(C, h, 1, 1, generator=g) / math.sqrt(h)
+    xs = [rnd((2, C, 12, 20), 10 + i, dtype) for i in range(3)]
+    w = torch.cat([sd["c.%s.%d.weight" % (fc, i)].reshape(-1) for fc in ("fc_avg_cf1", "fc_avg_cf2", "fc_max_cf1", "fc_max_cf2") for i in (0, 2)])
+    want = cfen_oracle.cfsm2g({k: v.double() for k, v in sd.items()}, "c", *[x.double() for x in xs])
+    d = dev()
+    xn = [ops.to_nhwc(x).to(d) for x in xs]
+    close(ops.from_nhwc(ops.cfsm2g(xn[0], xn[1], xn[2], w.to(d), C), C), want, tol(dtype, 4))
+
+
+@pytest.mark.parametrize("dh", [4, 12])
+def test_attention_fp32_only_head_dims(dh):
+    """head dims the net accepts in fp32 only (fragment width 4, not fp16's 8): n_feats 16 at 16 heads (4), n_feats 24 at 8 heads (12)"""
+    for S, heads, nseq in ((1, 16, 2), (16, 4, 3), (64, 8, 2), (256, 4, 2)):
+        qkv = rnd((nseq * S, 3 * heads * dh), 7 + S, torch.float32, 1.5)
+        close(ops.attention(qkv.to(dev()), nseq, S, heads), attn_ref(qkv, nseq, S, heads), tol(torch.float32, 3), "S %d dh %d" % (S, dh))

@@ -21,6 +21,12 @@ CASES = {
     "crs_full256_nf24_hdr4": NetConfig(24, 4, patch_size=32, load_size=256, variant="crs"),
     "v5_tiny_nf24_hdr4": NetConfig(24, 4, patch_size=8, load_size=64, variant="v5"),         # networks_iid_hlgvit_crs_gd4_cfs_v5.py
     "v5_full512_nf24_hdr4": NetConfig(24, 4, patch_size=32, load_size=256, variant="v5"),
+    # off n_feats 24: the CLI defaults (n_feats 32, hidden_dim_ratio 6), an odd ratio, n_feats 8, and 8 heads
+    "tiny_nf32_hdr6": NetConfig(32, 6, patch_size=8, load_size=64),
+    "full512_nf32_hdr6": NetConfig(32, 6, patch_size=32, load_size=256),
+    "tiny_nf16_hdr3": NetConfig(16, 3, patch_size=8, load_size=64),
+    "tiny_nf8_hdr4": NetConfig(8, 4, patch_size=8, load_size=64),
+    "tiny_nf32_hdr6_h8": NetConfig(32, 6, patch_size=8, load_size=64, num_heads=8),
 }
 N_KEYS = {"cfs": 934, "crs": 950, "v5": 1078}
 

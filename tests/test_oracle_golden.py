@@ -45,7 +45,7 @@ def test_oracle_v5_actnorm_first_call_takes_the_first_window():
 
 
 @pytest.mark.parametrize("name", ["tiny_nf24_hdr4", "tiny_nf24_hdr2", "small_nf24_hdr4", "cfs_tiny_nf24_hdr4", "crs_tiny_nf24_hdr4",
-                                  "v5_tiny_nf24_hdr4"])
+                                  "v5_tiny_nf24_hdr4", "tiny_nf32_hdr6", "tiny_nf16_hdr3", "tiny_nf8_hdr4", "tiny_nf32_hdr6_h8"])
 def test_oracle_small_nets(name):
     _run(name)
 
@@ -54,6 +54,18 @@ def test_oracle_small_nets(name):
 def test_oracle_full512():
     outs = _run("full512_nf24_hdr4")
     assert outs[0].shape == (1, 3, 512, 512) and outs[1].shape == (1, 1, 512, 512)
+
+
+@pytest.mark.slow
+def test_oracle_full512_at_the_cli_defaults():
+    """--n_feats 32 --hidden_dim_ratio 6 (options/base_options.py) at a 512 x 512 image: what test.py runs without those two flags"""
+    outs = _run("full512_nf32_hdr6")
+    assert outs[0].shape == (1, 3, 512, 512)
+
+
+def test_fixture_num_heads_defaults_to_the_reference_default():
+    assert load_net_fixture("tiny_nf24_hdr4")[0].num_heads == 4
+    assert load_net_fixture("tiny_nf32_hdr6_h8")[0].num_heads == 8
 
 
 @pytest.mark.slow

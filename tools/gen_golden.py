@@ -62,6 +62,14 @@ CONFIGS = {
     "refinit_v5_tiny_nf24_hdr4": (NetConfig(24, 4, patch_size=8, load_size=64, variant="v5"), 2, True),
     "refinit_tiny_nf24_hdr4": (NetConfig(24, 4, patch_size=8, load_size=64), 2, True),
     "refinit_full512_nf24_hdr4": (NetConfig(24, 4, patch_size=32, load_size=256), 1, False),
+    # off n_feats 24, where none of the fused fast paths apply: the CLI's own defaults (--n_feats 32 --hidden_dim_ratio 6,
+    # options/base_options.py) at a tiny image and at what test.py runs on a 512 x 512 image, an odd ratio (hidden % 64 != 0),
+    # n_feats 8 (D = 32: 64-byte fp16 token rows, a 4-channel head) and num_heads 8 (LViT head dim 16, GViT head dim 64)
+    "tiny_nf32_hdr6": (NetConfig(32, 6, patch_size=8, load_size=64), 2, True),
+    "full512_nf32_hdr6": (NetConfig(32, 6, patch_size=32, load_size=256), 1, False),
+    "tiny_nf16_hdr3": (NetConfig(16, 3, patch_size=8, load_size=64), 2, True),
+    "tiny_nf8_hdr4": (NetConfig(8, 4, patch_size=8, load_size=64), 1, True),
+    "tiny_nf32_hdr6_h8": (NetConfig(32, 6, patch_size=8, load_size=64, num_heads=8), 2, True),
 }
 
 
@@ -216,6 +224,8 @@ def gen_net(v3, common, name):
     if not name.startswith("refinit") and not batch_fixture:
         dump_manifest(net, os.path.join(GOLD, "state_manifest_%s.txt" % name))
     data = {"batch": np.int64(batch), "cfg": np.array([cfg.n_feats, cfg.hidden_dim_ratio, cfg.patch_size, cfg.load_size], np.int64)}
+    if cfg.num_heads != 4:              # fixtures without this key were made at the reference default of 4 heads
+        data["num_heads"] = np.int64(cfg.num_heads)
     names = stage_names(cfg.variant)
     assert len(names) == (54 if cfg.full_res else 58) and all(n in stages for n in names), [n for n in names if n not in stages]
     data["stage_names"] = np.array(names)
