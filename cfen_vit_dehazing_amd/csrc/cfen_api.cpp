@@ -289,6 +289,11 @@ int cfen_u8hwc_to_nhwc(int dtype, const unsigned char* in, void* out, int B, int
 int cfen_tensor2im_u8(const float* in, unsigned char* out, int C, int H, int W, void* stream) {
   return cfen_tensor2im_u8_impl(in, out, C, H, W, (hipStream_t)stream);
 }
+size_t cfen_image_metrics_bytes(int B, int C, int H, int W) { return cfen_image_metrics_bytes_impl(B, C, H, W); }
+int cfen_image_metrics(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
+                       void* stream) {
+  return cfen_image_metrics_impl(u8, a, b, B, C, H, W, lo, hi, scratch, out, (hipStream_t)stream);
+}
 int cfen_tile_gather(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, void* stream) {
   return cfen_tile_gather_impl(u8, src, dst, H, W, T, ny, nx, t0, B, (hipStream_t)stream);
 }

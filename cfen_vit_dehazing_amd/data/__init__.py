@@ -62,6 +62,26 @@ def get_transform(opt):
     raise NotImplementedError("--resize_or_crop %s uses random crops (training only)" % mode)
 
 
+def pair_ground_truth(hazy_paths, gt_dir):
+    """--eval: {hazy path: ground-truth path}.  The partner of a hazy image is the file of --gt_dir with the same stem (any image extension), else
+    the one whose stem is the hazy stem up to its first '_' (RESIDE: hazy/1400_1.png -> clear/1400.png).  ValueError naming the first hazy image
+    without a partner: raised when the dataset is built, before any forward."""
+    if not os.path.isdir(gt_dir):
+        raise ValueError("--eval: the ground-truth directory %s does not exist (--gt_dir, default <dataroot>/clear)" % gt_dir)
+    by_stem = {}
+    for path in sorted(make_dataset(gt_dir)):
+        by_stem.setdefault(os.path.splitext(os.path.basename(path))[0], path)
+    pairs = {}
+    for hazy in hazy_paths:
+        stem = os.path.splitext(os.path.basename(hazy))[0]
+        gt = by_stem.get(stem) or by_stem.get(stem.split('_', 1)[0])
+        if gt is None:
+            raise ValueError("--eval: no ground truth for %s in %s (looked for the stem '%s' and for '%s', with any image extension)"
+                             % (hazy, gt_dir, stem, stem.split('_', 1)[0]))
+        pairs[hazy] = gt
+    return pairs
+
+
 class DECVITDATA(torch.utils.data.Dataset):
     def initialize(self, opt):
         self.opt = opt
@@ -81,6 +101,8 @@ class DECVITDATA(torch.utils.data.Dataset):
             self.B_paths = shard_items(self.B_paths[:limit], world, rank)
         self.B_size = len(self.B_paths)
         self.transform = get_transform(opt)
+        # --eval: every hazy image needs its ground truth (the reference's training-mode folder `clear`, data/dec_vit_data.py:20), found now
+        self.A_of = pair_ground_truth(self.B_paths, getattr(opt, 'gt_dir', None) or os.path.join(opt.dataroot, 'clear')) if getattr(opt, 'eval', False) else None
 
     def __getitem__(self, index):
         if self.opt.sb:
@@ -93,7 +115,15 @@ class DECVITDATA(torch.utils.data.Dataset):
             raise ValueError("--u8_input hands over the decoded RGB image; single-channel input (--input_nc / --output_nc 1) needs the float path")
         if gray:
             B = (B[0, ...] * 0.299 + B[1, ...] * 0.587 + B[2, ...] * 0.114).unsqueeze(0)
-        return {'B': B, 'B_paths': B_path}
+        if getattr(self, 'A_of', None) is None:
+            return {'B': B, 'B_paths': B_path}
+        # --eval: the ground truth as decoded, (H,W,3) uint8, under the reference's training-mode keys 'A' / 'A_paths' (data/dec_vit_data.py:60-119)
+        A_path = self.A_of[B_path]
+        A = to_u8_hwc(Image.open(A_path).convert('RGB'))
+        size_B = tuple(B.shape[:2]) if B.dtype == torch.uint8 else tuple(B.shape[1:])
+        if tuple(A.shape[:2]) != size_B:
+            raise ValueError("--eval: the ground truth %s is %d x %d but the output for %s is %d x %d" % ((A_path,) + tuple(A.shape[:2]) + (B_path,) + size_B))
+        return {'B': B, 'B_paths': B_path, 'A': A, 'A_paths': A_path}
 
     def __len__(self):
         return self.B_size

@@ -37,6 +37,9 @@ class DECHLGVIT(BaseModel):
         else:
             B = B.to(self.device)
         self.image_paths = input['B_paths']
+        # --eval: the ground truth of this batch, (B,H,W,3) uint8 (data/__init__.py), scored against fake_A after test()
+        self._gt = input['A'].to(self.device) if 'A' in input else None
+        self._gt_paths = list(input['A_paths']) if 'A' in input else []
         if B.dtype == torch.uint8:
             # --u8_input: (B,H,W,3) uint8 goes to the generator as it is (normalised by the plan's first launch);
             # `real_B` of get_current_visuals stays what the reference shows: the normalised float image
@@ -81,9 +84,36 @@ class DECHLGVIT(BaseModel):
         self._u8_out = not getattr(opt, 'isTrain', False) and getattr(opt, 'phase', 'test') == 'test' and hasattr(self.netG, 'output_u8')
         # --tile: every image runs as overlapping image_size x image_size tiles (tiled.py, any input size); the fp32 comparison above is not extended to them
         self._tile = bool(getattr(opt, 'tile', False))
+        self._eval = bool(getattr(opt, 'eval', False))
+        self._metrics = {}
         if self._tile and self._half_guard:
             print('notice: --precision half with --tile: the fp32 guard does not cover tiled images; they run in fp16 unchecked')
             self._half_guard = False
+
+    # ---- --eval: PSNR / SSIM of the written bytes against the ground truth, on the device (metrics.py) ------------------------------------------------
+    def test(self, opt=None):
+        BaseModel.test(self, opt)
+        if getattr(self, '_eval', False):
+            self._score()
+
+    def _score(self):
+        from .. import metrics, ops
+        out = self.fake_A
+        if out.dtype != torch.uint8:
+            # float outputs (no u8 output mode, or the fp32 side of a failed half guard): the bytes save_images will write, from the same device pass
+            out = torch.stack([ops.tensor2im_u8(out[b].float().contiguous()) for b in range(out.shape[0])])
+        gt = getattr(self, '_gt', None)
+        if gt is None:
+            raise RuntimeError('--eval: the dataset handed over no ground truth (key A) for %s' % (list(self.image_paths),))
+        if tuple(out.shape) != tuple(gt.shape):
+            raise ValueError('--eval: the ground truth %s is %d x %d but the output for %s is %d x %d'
+                             % (self._gt_paths[0], gt.shape[1], gt.shape[2], self.image_paths[0], out.shape[1], out.shape[2]))
+        for path, (p, s) in zip(self.image_paths, metrics.psnr_ssim(out, gt)):
+            self._metrics[path] = (p, s)           # an image run again (redone in fp32 after a failed half guard) replaces its row, in place
+
+    def current_metrics(self):
+        """[(hazy image path, psnr, ssim), ...] of every image scored so far, in the order they first ran"""
+        return [(path, p, s) for path, (p, s) in getattr(self, '_metrics', {}).items()]
 
     def _guard_dir(self):
         import os

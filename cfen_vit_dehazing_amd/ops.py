@@ -382,6 +382,34 @@ def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False):
     return outs
 
 
+def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
+    """cfen_image_metrics: per image pair (sse, ssim) as two float64 CUDA tensors of shape (B,), in one fused pass.
+
+    a, b: (B,H,W,3) uint8, scored as v / 255, or (B,C,H,W) float32 with C 1 or 3, scored as (v - lo) / (hi - lo) for value_range = (lo, hi); an
+    image without the batch dimension is taken as a batch of one.  ssim is the reference's pytorch_msssim.ssim(window_size=11, val_range=1): Gaussian
+    window, valid convolution, mean over channels and window positions.  sse is the sum of squared differences on the 0..255 scale over all values
+    (exact for uint8); metrics.psnr_from_sse turns it into PSNR.  H, W >= 11."""
+    _cuda(a, b)
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
+        raise ValueError("image_metrics: the two images differ in shape, dtype or device: %s %s against %s %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    u8 = a.dtype == torch.uint8
+    if a.dim() != 4 or (u8 and a.shape[3] != 3) or (not u8 and (a.dtype != torch.float32 or a.shape[1] not in (1, 3))):
+        raise ValueError("image_metrics needs (B,H,W,3) uint8 or (B,1|3,H,W) float32 images, got %s %s" % (tuple(a.shape), a.dtype))
+    B, C, H, W = (a.shape[0], 3, a.shape[1], a.shape[2]) if u8 else tuple(a.shape)
+    lib = _lib.load()
+    nbytes = lib.cfen_image_metrics_bytes(B, C, H, W)
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=a.device)
+    if out is None:
+        out = torch.empty(B, 2, dtype=torch.float64, device=a.device)
+    elif tuple(out.shape) != (B, 2) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("image_metrics: out must be a contiguous (%d, 2) float64 CUDA tensor" % B)
+    lo, hi = value_range
+    check(lib.cfen_image_metrics(int(u8), ptr(a), ptr(b), B, C, H, W, float(lo), float(hi), ptr(scratch), ptr(out), current_stream()), "image_metrics")
+    return out[:, 0], out[:, 1]      # (scratch goes back to torch's allocator on the stream it was used on)
+
+
 def u8hwc_to_nhwc(img, cs, dtype):
     """(B,H,W,3) uint8 CUDA tensor -> normalised NHWC [B,H,W,cs] of `dtype` (ToTensor + Normalize(0.5, 0.5) + layout)"""
     _cuda(img)

@@ -84,6 +84,12 @@ class BaseOptions():
                             'back to the input size (cfen_vit_dehazing_amd/tiled.py); needs --batchSize 1 and --in_flight 1')
         p.add_argument('--tile_overlap', type=int, default=None, help='(extension) --tile: overlap of neighbouring tiles in pixels (default image_size // 8)')
         p.add_argument('--tile_batch', type=int, default=8, help='(extension) --tile: tiles per forward')
+        p.add_argument('--eval', action='store_true',
+                       help='(extension) score every dehazed image against its ground truth on the device: per-image PSNR (RGB, 10 log10(1 / MSE)) and SSIM '
+                            '(the reference\'s pytorch_msssim.ssim, 11 x 11 Gaussian window, valid convolution) of the very bytes written to the PNG, into '
+                            'results/<name>/<phase>_<epoch>/metrics.csv; needs --sb and --in_flight 1')
+        p.add_argument('--gt_dir', type=str, default=None,
+                       help='(extension) --eval: folder of ground-truth images, paired by stem or by the stem up to its first "_" (default <dataroot>/clear)')
         p.add_argument('--patch_dim', type=int, default=2)
         p.add_argument('--num_heads', type=int, default=4)
         p.add_argument('--num_layers', type=int, default=1)
@@ -125,6 +131,13 @@ class BaseOptions():
                                  '(got --batchSize %d --in_flight %d)' % (opt.batchSize, opt.in_flight))
             if opt.tile_batch < 1:
                 raise ValueError('--tile_batch must be >= 1')
+        if getattr(opt, 'eval', False):
+            if opt.in_flight != 1:
+                raise ValueError('--eval scores the images of the sequential loop: it needs --in_flight 1 (got --in_flight %d); the pipelined driver '
+                                 'does not compute metrics' % opt.in_flight)
+            if not opt.sb:
+                raise ValueError('--eval needs --sb: without it the images are sampled randomly (dec_vit_data.py:51-58) and metrics.csv would not '
+                                 'cover the dataset in order')
         if not -1 <= opt.png_compress_level <= 9:
             raise ValueError('--png_compress_level must be -1 (PIL default) or 0..9')
         from ..util import util as _util
@@ -137,6 +150,8 @@ class BaseOptions():
         if len(opt.gpu_ids) > 0 and torch.cuda.is_available():
             torch.cuda.set_device(opt.gpu_ids[0])
         args = vars(opt)
+        if not getattr(opt, 'eval', False):
+            args = {k: v for k, v in args.items() if k not in ('eval', 'gt_dir')}      # a run without --eval prints and records what it always did
         if opt.dist_rank == 0:
             print('------------ Options -------------')
             for k, v in sorted(args.items()):

@@ -310,6 +310,23 @@ int cfen_tile_gather(int u8, const void* src, void* dst, int H, int W, int T, in
 int cfen_tile_blend(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs, void* xd,
                     void* stream);
 
+/* Image quality of an output against its ground truth, per image pair, in one fused pass (csrc/k_metrics.hip; metrics.py, test.py --eval).
+ * Both images are scored on the [0,1] scale in fp32, data range L = 1:
+ *   u8 = 1: a, b (B,H,W,3) uint8, v -> v / 255 (C must be 3);  u8 = 0: a, b (B,C,H,W) fp32, C 1 or 3, v -> (v - lo) / (hi - lo), e.g. (-1, 1)
+ *           for the generator's float outputs (lo / hi are ignored for uint8).
+ *   SSIM: pytorch_msssim.ssim(window_size = 11, size_average = True, val_range = 1) of the reference (pytorch_msssim/__init__.py:19-70): 11 x 11
+ *         Gaussian window, sigma 1.5, normalised; VALID convolution (no padding); C1 = 0.01^2, C2 = 0.03^2; the mean over all C (H - 10) (W - 10)
+ *         window positions.  H, W >= 11: the reference shrinks its window for smaller images, this library refuses them (CFEN_ERR_ARG).
+ *   SSE : the sum over all C H W values of (255 (a - b))^2, i.e. on the 0..255 scale in both formats; for uint8 input it is summed in integers and
+ *         is exact.  PSNR = 10 log10(255^2 C H W / SSE) = 10 log10(1 / MSE on the [0,1] scale) is left to the caller (metrics.py; inf when SSE = 0):
+ *         the standard definition over the RGB values, not the Y channel -- the reference has no PSNR code.
+ * out: [B][2] doubles on the device, (SSE, SSIM mean) per pair, 8-byte aligned.  scratch: cfen_image_metrics_bytes(B, C, H, W) bytes of device
+ * memory, 8-byte aligned, contents irrelevant before and after (one (SSE, SSIM sum) pair per workgroup tile; 0 for dimensions the call refuses).
+ * No atomics, fixed summation order in fp64: the same inputs give the same bits on every call, stream and batch size.                        */
+size_t cfen_image_metrics_bytes(int B, int C, int H, int W);
+int cfen_image_metrics(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
+                       void* stream);
+
 /* Conv2d / ConvTranspose2d(4,2,1) as implicit GEMM with fused affine + activation + residuals.
  * kind 0: Conv2d(k, stride, pad) over nsrc (1..3) channel-concatenated inputs (src0 | src1 | src2, the concat is never
  * materialised: v3:488 torch.cat((local, global), 1); crs_gd4:854 cat of three); kind 1: ConvTranspose2d k4 s2 p1.

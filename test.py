@@ -6,6 +6,7 @@
 
 Loads checkpoints/<name>/<which_epoch>_net_G.pth (the reference's own file format), runs the HIP generator on
 every image of <dataroot>/hazy and writes results/<name>/<phase>_<which_epoch>/images/<stem>_fake_A.png.
+With --eval every image is also scored against <dataroot>/clear (PSNR, SSIM) into results/<name>/<phase>_<which_epoch>/metrics.csv.
 """
 import logging
 import os
@@ -125,6 +126,21 @@ if __name__ == '__main__':
         _rerun_in_fp32(opt, model, webpage.get_image_dir(), model.redo_paths)
     if opt.in_flight > 1 and getattr(opt, 'writer_procs', 0) > 0:
         _pipeline.stop_writer_processes()
+    if getattr(opt, 'eval', False):
+        # per-image PSNR / SSIM of the written bytes (scored on the device after every test(), models/model_iid_dehazing.py): one metrics.csv in dataset
+        # order; under torch.distributed.run the ranks hold consecutive slices, rank 0 gathers their rows over the gloo group and writes the file
+        from cfen_vit_dehazing_amd import metrics as _metrics
+        rows = [(os.path.basename(p), a, b) for p, a, b in model.current_metrics()]
+        if opt.dist_world > 1:
+            import torch.distributed as dist
+            gathered = [None] * opt.dist_world if opt.dist_rank == 0 else None
+            dist.gather_object(rows, gathered, dst=0)
+            rows = [r for part in gathered for r in part] if opt.dist_rank == 0 else []
+        if opt.dist_rank == 0:
+            with open(os.path.join(web_dir, 'metrics.csv'), 'w') as f:
+                f.write(_metrics.format_csv(rows))
+            print(_metrics.summary_line(rows))
+            print('eval: wrote %s' % os.path.join(web_dir, 'metrics.csv'))
     if opt.dist_world > 1:
         import torch.distributed as dist
         dist.barrier()
