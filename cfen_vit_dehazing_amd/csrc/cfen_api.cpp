@@ -27,13 +27,8 @@ CfenGraphRecorder*& cfen_recorder() {
   static thread_local CfenGraphRecorder* rec = nullptr;
   return rec;
 }
-// zero `bytes` of device memory on a lane: eagerly, or as a memset node of the graph being built
-// Zeroing of synchronisation words (split-K arrival counters, the chains' barrier words) in front of the launches that use them.
-// MEASURED (round 4, MI355X, ROCm 7.2): as a hipGraph MEMSET node -- dependencies recorded like every kernel node's -- the zeroing is NOT ordered against its
-// neighbouring kernel nodes once several instantiated graphs are in flight on different streams: counters were cleared in the middle of a launch that was
-// counting arrivals (outputs off by 0.07 .. 0.2, no wait gave up), one graph at a time it is fine.  As a kernel node it is ordered.  "net.zero_memset" = 1 is the
-// old form, kept for the A/B (tests/test_hip_net.py::test_three_forwards_in_flight...; profiles/r04_ab_zero_memset.txt).
-int& cfen_tune_zero_memset() { static int v = 0; return v; }
+// zero `bytes` of device memory on a lane: by a kernel (why: "net.zero_memset" in cfen_tune_knobs.hpp) or, with that knob on, by a memset --
+// eagerly, or as a memset node of the graph being built
 int cfen_zero_async(void* p, size_t bytes, hipStream_t s) {
   CFEN_CHECK_ARG(p && bytes % 4 == 0, "zero_async: bad region");
   if (!cfen_tune_zero_memset()) return cfen_zero_words_impl(p, bytes / 4, s);   // a kernel (node): ordered like every other launch of the plan
@@ -302,204 +297,7 @@ int cfen_tile_blend(int dtype, const void* arena, int B, int T, int H, int W, in
   return cfen_tile_blend_impl(dtype, arena, B, T, H, W, ny, nx, overlap, out_u8, xr, xs, xd, (hipStream_t)stream);
 }
 
-int cfen_tune(const char* key, int value) {
-  CFEN_CHECK_ARG(key != nullptr, "tune: null key");
-  if (!strcmp(key, "gemm.kernel")) {
-    CFEN_CHECK_ARG(value >= -1 && value <= 25, "tune: gemm.kernel must be -1 .. 25");
-    cfen_tune_gemm_kernel() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.large") || !strcmp(key, "gemm.small") || !strcmp(key, "gemm.mid")) {
-    CFEN_CHECK_ARG(value == 2 || value == 3 || value == 4 || value == 5 || value == 12 || value == 13 || value == 14 || value == 15 || value == 22 || value == 23 ||
-                   value == 24 || value == 25 || value == 32 || value == 34 || value == 45 || value == 65,
-                   "tune: %s must be tile 2 .. 5 (+10 / +20 for 3 / 4 LDS stages; 34 = tile 4 with 5 stages, 45 / 65 = tile 5 with 6 / 8 stages)", key);
-    (key[5] == 'l' ? cfen_tune_gemm_large() : key[5] == 'm' ? cfen_tune_gemm_mid() : cfen_tune_gemm_small()) = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.big")) {
-    CFEN_CHECK_ARG(value == 0 || value == 6, "tune: gemm.big is 0 (off) or 6 (192 x 128 tiles)");
-    cfen_tune_gemm_big() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "convT.tpw")) {
-    CFEN_CHECK_ARG(value >= 1, "tune: convT.tpw must be >= 1");
-    cfen_tune_convT_tpw() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "conv7.tpw")) {
-    CFEN_CHECK_ARG(value >= 1, "tune: conv7.tpw must be >= 1");
-    cfen_tune_conv7_tpw() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "conv.wlds") || !strcmp(key, "conv.wlds_maxlog")) {
-    CFEN_CHECK_ARG(value >= 0, "tune: %s must be >= 0", key);
-    (key[9] ? cfen_tune_conv_wlds_maxlog() : cfen_tune_conv_wlds()) = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.big_min_tiles")) {
-    CFEN_CHECK_ARG(value >= 1, "tune: gemm.big_min_tiles must be positive");
-    cfen_tune_gemm_big_min_tiles() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "embed.lds")) {
-    cfen_tune_embed_lds() = value & 7;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "embed.stages")) {
-    CFEN_CHECK_ARG(value >= 2 && value <= 5, "tune: embed.stages is 2 .. 5 ring stages of k_embed_qkv2 (D = 192)");
-    cfen_tune_embed_stages() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "mlp3.tm192")) {
-    CFEN_CHECK_ARG((value >= 2 && value <= 4) || value == 22 || value == 24 || value == 25 || value == 28, "tune: mlp3.tm192 is 2, 3 or 4 token tiles a wave (one workgroup a CU), 22 / 24 = 2 tiles at 256 registers on a 3- / 4-slot ring");
-    cfen_tune_mlp3_tm192() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "embed.defer_refill")) {
-    cfen_tune_embed_defer_refill() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.defer_refill")) {
-    cfen_tune_gemm_defer_refill() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "lvit.debug")) {
-    cfen_tune_lvit_debug() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "front3.debug")) {
-    cfen_tune_front3_debug() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "mlp3.pair")) {
-    cfen_tune_mlp3_pair() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "mlp3.debug")) {
-    cfen_tune_mlp3_debug() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.m128")) {
-    CFEN_CHECK_ARG(value == 0 || value == 2 || value == 32 || value == 3 || value == 4 || value == 14 || value == 34, "tune: gemm.m128 is 0 or a k_gemm_dma tile id");
-    cfen_tune_gemm_m128() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.splitk_stages")) {
-    CFEN_CHECK_ARG(value == 0 || value == 3, "tune: gemm.splitk_stages is 0 or 3");
-    cfen_tune_gemm_splitk_stages() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.splitk_release")) { cfen_tune_gemm_splitk_release() = value; return CFEN_OK; }
-  if (!strcmp(key, "gemm.splitk")) {
-    cfen_tune_gemm_splitk() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.ln_fold")) {
-    cfen_tune_ln_fold() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.fused_front_max_dim")) {
-    cfen_tune_fused_front_max_dim() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.skip_classes")) {
-    cfen_tune_skip_classes() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "mlp.small_tiles")) {
-    cfen_tune_mlp_small_tiles() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "lvit.shape")) {
-    cfen_tune_lvit_shape() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.lvit_window")) {
-    cfen_tune_lvit_window() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.fold_in_gemm")) {
-    cfen_tune_fold_in_gemm() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.attn_head_major")) {
-    cfen_tune_attn_head_major() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "dcn.tps")) {
-    cfen_tune_dcn_tps() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gemm.nt")) {
-    cfen_tune_gemm_nt() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "dcn.tile")) {
-    cfen_tune_dcn_tile() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "attn.hm_pair")) {
-    cfen_tune_attn_hm_pair() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.head_fused")) {
-    cfen_tune_head_fused() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.stream_front")) {
-    CFEN_CHECK_ARG(value >= 0 && value <= 2, "tune: net.stream_front is 0 (never), 1 (grouped decoder launches) or 2 (always)");
-    cfen_tune_stream_front() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.stream_mlp192")) {
-    cfen_tune_stream_mlp192() = value != 0;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.stream_mlp")) {
-    CFEN_CHECK_ARG(value >= 0 && value <= 2, "tune: net.stream_mlp is 0 (never), 1 (grouped decoder launches) or 2 (always)");
-    cfen_tune_stream_mlp() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.gvit_dummy_wgs")) { cfen_tune_gvit_dummy_wgs() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.gvit_dummy_us")) { cfen_tune_gvit_dummy_us() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.skip_from")) { cfen_tune_skip_from() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.skip_to")) { cfen_tune_skip_to() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.extra_launches")) { cfen_tune_extra_launches() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.gvit_dummy_levels")) { cfen_tune_gvit_dummy_levels() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.gvit_dummy_stream")) { cfen_tune_gvit_dummy_stream() = value; return CFEN_OK; }
-  if (!strcmp(key, "gvit.team")) {
-    CFEN_CHECK_ARG(value >= 1 && value <= 85, "tune: gvit.team is 1 .. 85 workgroups per block (three blocks share the chip)");
-    cfen_tune_gvit_team() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.gvit_stream")) {
-    CFEN_CHECK_ARG(value >= 0 && value <= 2, "tune: net.gvit_stream is 0 (never), 1 (serial launch plan only) or 2 (every plan)");
-    cfen_tune_gvit_stream() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "gvit.max_concurrent")) {
-    CFEN_CHECK_ARG(value >= 1 && value <= 8, "tune: gvit.max_concurrent is 1 .. 8 forwards in flight");
-    cfen_tune_gvit_max_concurrent() = value;
-    return CFEN_OK;
-  }
-  if (!strcmp(key, "net.tail_fused")) { CFEN_CHECK_ARG(value >= 0 && value <= 2, "tune: net.tail_fused is 0, 1 (ConvTranspose + 3x3) or 2 (+ the 7x7)"); cfen_tune_tail_fused() = value; return CFEN_OK; }
-  if (!strcmp(key, "tail.balance")) { cfen_tune_tail_balance() = value; return CFEN_OK; }
-  if (!strcmp(key, "tail.debug")) { cfen_tune_tail_debug() = value; return CFEN_OK; }
-  if (!strcmp(key, "tail.segments")) { CFEN_CHECK_ARG(value >= 1 && value <= 64, "tune: tail.segments is 1 .. 64"); cfen_tune_tail_segments() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.up_fused")) { cfen_tune_up_fused() = value != 0; return CFEN_OK; }
-  if (!strcmp(key, "net.zero_memset")) { cfen_tune_zero_memset() = value != 0; return CFEN_OK; }
-  if (!strcmp(key, "net.keep_stages")) { cfen_tune_keep_stages() = value != 0; return CFEN_OK; }
-  if (!strcmp(key, "net.resblock_fused")) { cfen_tune_resblock_fused() = value != 0; return CFEN_OK; }
-  if (!strcmp(key, "net.head5")) { cfen_tune_head5() = value != 0; return CFEN_OK; }
-  if (!strcmp(key, "gvit.debug")) { cfen_tune_gvit_debug() = value; return CFEN_OK; }
-  if (!strcmp(key, "net.gvit_chain")) { cfen_tune_gvit_chain() = value; return CFEN_OK; }   // 0 off, 1 every GViT block, 2 the grouped decoder launches only, 3 the encoder blocks only
-  if (!strcmp(key, "net.embed_gather")) {
-    cfen_tune_embed_gather() = value != 0;
-    return CFEN_OK;
-  }
-  cfen_set_error("tune: unknown key '%s'", key);
-  return CFEN_ERR_ARG;
-}
+// cfen_tune / cfen_tune_query / cfen_tune_key: cfen_tune.cpp, from the table in cfen_tune_knobs.hpp
 
 int cfen_conv2d(int dtype, const cfen_conv_args* a, void* stream) {
   CFEN_CHECK_ARG(a != nullptr, "conv2d: null args");

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cfen_tune_knobs.hpp"   // lvit.shape, lvit.debug
+
 struct LvitArgs {
   const void* fmap; void* out;            // NHWC maps (B, H, W), channel strides cs_in / cs_out, C real channels
   int B, H, W, C, cs_in, cs_out, ws, p;   // window edge ws (32), patch p (2): 256 tokens of D = p*p*C = 96 per window
@@ -19,4 +21,3 @@ struct LvitArgs {
 
 bool cfen_lvit_window_supported(int dtype, int D, int heads, int S, int hidden);
 int cfen_lvit_window_impl_g(int dtype, int ng, const LvitArgs* a, hipStream_t s);
-int& cfen_tune_lvit_shape();

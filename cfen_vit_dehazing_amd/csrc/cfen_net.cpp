@@ -20,68 +20,6 @@
 #include "cfen_mlp.hpp"
 #include "cfen_lvit.hpp"
 
-int& cfen_tune_skip_classes() {
-  static int v = 0;
-  return v;
-}
-int& cfen_tune_gvit_dummy_wgs() { static int v = 0; return v; }
-int& cfen_tune_gvit_dummy_us() { static int v = 100; return v; }
-int& cfen_tune_gvit_dummy_stream() { static int v = 0; return v; }
-int& cfen_tune_skip_from() { static int v = -1; return v; }   // what-if probe: the launches number skip_from .. skip_to of a forward are not launched (outputs invalid)
-int& cfen_tune_skip_to() { static int v = -1; return v; }
-int& cfen_tune_extra_launches() { static int v = 0; return v; }   // what-if probe: that many one-workgroup 1 us launches in front of every ViT block (what a launch costs a chain)
-int& cfen_tune_gvit_dummy_levels() { static int v = 0; return v; }   // 1: the what-if probe replaces only the blocks that run as a launch per GEMM (levels 2-3)
-int& cfen_tune_gvit_chain() { static int v = 1; return v; }   // only nets built with fragment-stream GViT weights (cfg.reserved bit 2) can use it
-int& cfen_tune_gvit_stream() { static int v = 2; return v; }   // 0 never, 1 in the serial launch plan only, 2 (default, round 5) on every plan: which KERNELS produce the
-                                                                // outputs no longer depends on the lane plan or on profiling (two-lane, serial and profiled forwards are bitwise equal;
-                                                                // the stream kernels cost one forward at a time 2.80 -> 2.85 ms and gain 2.27 -> 2.24 with several in flight)
-                                                                // (one forward at a time on the two-lane plan it is SLOWER, 2.85 against 2.80 ms: 277 us of latency against 134)
-int& cfen_tune_tail_fused() { static int v = 2; return v; }   // 0 three launches, 1 ConvTranspose + 3x3 fused (round 4), 2 (default, round 5) the whole tail in one launch (k_tail.hip)
-int& cfen_tune_up_fused() { static int v = 0; return v; }
-int& cfen_tune_keep_stages() { static int v = 0; return v; }
-int& cfen_tune_resblock_fused() { static int v = 0; return v; }   // 0 (default): MEASURED with three forwards in flight 2.44 against 2.48 ms -- the fused kernel (5-wave workgroups, 58 KB of LDS, 154 registers) is 13 us shorter alone and costs more CU-time beside other forwards
-int& cfen_tune_head5() { static int v = 1; return v; }
-int& cfen_tune_ln_fold() {
-  static int v = 1;
-  return v;
-}
-int& cfen_tune_fused_front_max_dim() {
-  static int v = 192;
-  return v;
-}
-int& cfen_tune_embed_gather() {
-  static int v = 1;
-  return v;
-}
-int& cfen_tune_lvit_window() {
-  static int v = 1;
-  return v;
-}
-int& cfen_tune_fold_in_gemm() {   // 1 (default): mlp_head.3's GEMM stores straight into the NHWC map (fold + Join2x2), no unpatchify launch
-  static int v = 1;
-  return v;
-}
-int& cfen_tune_attn_head_major() {
-  static int v = 1;
-  return v;
-}
-int& cfen_tune_head_fused() {   // 0 (default): three k_conv_tile launches.  MEASURED (MI355X, batch 8): k_head_fused moves 100 MB instead of 400 MB and is
-  static int v = 0;             // SLOWER, 131 us against 108: with 3 input channels padded to 8 and 5 taps to 8 its MFMA work is 5x the algorithmic
-  return v;                     // flops (22 % MFMA-busy, profiles/r03_*), and the unfused kernels already run at the HBM rate of their own maps
-}
-int& cfen_tune_stream_front() {   // k_front3 for the D = 384 LViT blocks: 0 never, 1 grouped decoder launches, 2 (default, round 4) always
-  static int v = 2;             // (with three forwards in flight the single encoder instance on the stream kernels is 0.03 ms better: one whole-CU launch of 64 workgroups instead of 8 GEMM launches)
-  return v;
-}
-int& cfen_tune_stream_mlp192() {   // LViT level 2 (D = 192) proj + MLP block: 1 (default, round 5) on k_mlp3 (fragment-stream weights, three-slot ring; mlp3.tm192 = 22: TWO 78 KB
-  static int v = 1;                // workgroups a CU at 256 registers -- k_mlp2's occupancy without its two-stage ring, whose chunk period is one LDS-DMA issue -> landed
-  return v;                        // latency: encoder 79.7 -> 56.4 us, grouped decoder launch 168.4 -> 128.2 us (961 TF), 2.148 -> 2.121 ms per step with four forwards in
-}                                  // flight, profiles/r05_ab_stream_mlp192_two_wgs_per_cu.txt); 0: k_mlp2.  (k_mlp3<12, 3> on one 150 KB workgroup a CU, rounds 3-4: equal to k_mlp2.)
-int& cfen_tune_stream_mlp() {   // k_mlp3 (k_stream.hip) for the D = 384 blocks: 0 never, 1 launches of >= 128 workgroups (at 512 x 512 the grouped
-  static int v = 2;             // decoder launch; a single instance has 64 workgroups of 128 tokens: a quarter of the chip), 2 (default, round 4) always
-  return v;
-}
-
 namespace {
 
 struct Param {

@@ -11,6 +11,7 @@
 // maps) and head_dim 24 is zero-padded to the MFMA K of 32 (fp16) / 2x16 (fp32).
 #include <stdlib.h>
 #include "cfen_common.hpp"
+#include "cfen_tune_knobs.hpp"   // attn.hm_pair
 
 namespace {
 
@@ -729,10 +730,6 @@ int cfen_attention_impl_g(int dtype, int ng, const void* const* qkv, void* const
   if (dtype == 0) return dispatch_attn<float>(ng, qkv, out, nseq, S, heads, dh, s);
   cfen_set_error("attention: unknown dtype %d", dtype);
   return CFEN_ERR_ARG;
-}
-int& cfen_tune_attn_hm_pair() {   // 1: 256-token windows run on k_attention_hm_long<16, 16> (two query tiles per K / V fragment, 8 waves); 2: 1024-token windows on 8 waves instead of 16
-  static int v = 0;
-  return v;
 }
 
 bool cfen_attention_hm_supported(int dtype, int S, int dh) { return dtype == 1 && dh == 24 && (S == 1024 || S == 256 || S == 64); }

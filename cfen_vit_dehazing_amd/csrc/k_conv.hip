@@ -413,14 +413,6 @@ int check_conv(const ConvDesc& d) {
 }
 
 }  // namespace
-int& cfen_tune_conv_wlds() {
-  static int v = 2;
-  return v;
-}
-int& cfen_tune_conv_wlds_maxlog() {   // staged weights only for launches below 2^this pixels
-  static int v = 40;
-  return v;
-}
 namespace {
 
 template <typename T>

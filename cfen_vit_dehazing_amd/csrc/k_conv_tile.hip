@@ -566,14 +566,6 @@ bool cfen_conv7_tz_supported(int dtype, int k, int stride, int pad, int nsrc, in
          W % 64 == 0;
 }
 int cfen_conv7_tz_kpad() { return Z_KPAD; }
-int& cfen_tune_convT_tpw() {   // tiles per workgroup of the 128-byte k_convT_tile variant ("convT.tpw")
-  static int v = 2;
-  return v;
-}
-int& cfen_tune_conv7_tpw() {   // tiles per workgroup of k_conv7_tz ("conv7.tpw")
-  static int v = 4;
-  return v;
-}
 
 int cfen_conv7_tz_impl_g(int dtype, int ng, const ConvDesc* dp, hipStream_t s) {
   CFEN_CHECK_ARG(ng >= 1 && ng <= CFEN_MAX_GROUPS && dp, "conv7 (toeplitz): 1..%d problems per launch", CFEN_MAX_GROUPS);

@@ -13,9 +13,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "cfen_common.hpp"
-
-int& cfen_tune_dcn_tile();
-int& cfen_tune_dcn_tps();
+#include "cfen_tune_knobs.hpp"   // dcn.tile, dcn.tps
 
 namespace {
 struct DcnArgs;
@@ -842,16 +840,6 @@ void dcn_use_scratch(int dtype, DcnArgs& a, void* columns, size_t columns_bytes)
 }
 
 }  // namespace
-
-int& cfen_tune_dcn_tile() {   // 1 (default): k_dcn_lean where its shapes allow; 0: k_dcn_nhwc (round 2)
-  static int v = 1;
-  return v;
-}
-
-int& cfen_tune_dcn_tps() {   // taps per K slice of k_dcn_lean at most this (0: as many as fit 60 KB of LDS) ("dcn.tps")
-  static int v = 0;
-  return v;
-}
 
 extern "C" {
 

@@ -657,20 +657,6 @@ int run_embed_qkv(int ng, const CfenEmbedQkvArgs* ap, hipStream_t s) {
 
 }  // namespace
 
-int& cfen_tune_embed_defer_refill() {   // k_embed_qkv2: 1 = refill behind the chunk's first fragment reads, 0 = right behind the barrier (rounds 2-5)
-  static int v = 1;
-  return v;
-}
-int& cfen_tune_embed_stages() {   // ring stages of k_embed_qkv2 at D = 192 ("embed.stages"): 2 (rounds 2-4), 3, 4 (default, round 5), 5
-  static int v = 4;
-  return v;
-}
-
-int& cfen_tune_embed_lds() {
-  static int v = 6;
-  return v;
-}
-
 bool cfen_embed_qkv_supported(int D) { return D == 96 || D == 192; }
 
 int cfen_embed_qkv_impl_g(int dtype, int ng, const CfenEmbedQkvArgs* a, hipStream_t s) {

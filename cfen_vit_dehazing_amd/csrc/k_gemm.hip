@@ -15,11 +15,6 @@
 #include "cfen_common.hpp"
 #include "cfen_internal.hpp"
 
-int& cfen_tune_gemm_nt();
-int& cfen_tune_gemm_defer_refill();
-int& cfen_tune_gemm_splitk_release();
-int& cfen_tune_gemm_mid();
-
 namespace {
 
 // XCD-aware block -> tile map.  Blocks are dealt round-robin to the 8 XCDs (own L2 each); XCD x = block & 7 works on one
@@ -755,59 +750,6 @@ int launch_gemm(int ng, const CfenGemmPtrs* gp, int ldx, int ldw, int ldr, int p
 
 float& cfen_gemm_lnf_eps() {
   static float v = 1e-5f;
-  return v;
-}
-int& cfen_tune_gemm_defer_refill() {   // k_gemm_dma: 1 = a K-step's refill behind its first fragment reads, 0 = right behind the barrier (rounds 2-5) ("gemm.defer_refill")
-  static int v = 1;
-  return v;
-}
-int& cfen_tune_gemm_nt() {   // weight rows of k_gemm_dma by non-temporal LDS-DMA: 0 never, 1 few-token GEMMs (M <= 512: GViT levels 2 and 3), 2 always ("gemm.nt")
-  static int v = 0;
-  return v;
-}
-
-int& cfen_tune_gemm_splitk() {   // 0 (default, round 4): with several forwards in flight the unsplit launches are faster (2.13 against 2.16 ms per step, and 2.80 with
-  static int v = 0;               // the release fence below: a split launch is more workgroups, and CU-time is what a forward costs there); 1 = round 3's shape rule
-  return v;
-}
-int& cfen_tune_gemm_splitk_release() {   // 1 (default): every K slice runs an agent-scope release fence before its arrival ticket -- the memory model's recipe;
-  static int v = 1;                       // 0 = round 3's publish (write-through slab stores + a vmcnt drain, the guide's "measured, not an architectural guarantee" row):
-  return v;                               // also right in every test here, 57.7 -> 22.0 us on a 1024-workgroup launch.  (Round 4 blamed this seam for wrong outputs with two
-}                                         // forwards in flight; the cause was the counters' zeroing as a graph MEMSET node, cfen_api.cpp: cfen_zero_async.)
-// 0 (default): off; 6: 192 x 128 tiles, 2-stage ring (80 KB of LDS, two workgroups a CU).  MEASURED (MI355X, B = 8, round 2): the
-// LViT-3 / GViT-1 qkv, ffn1, head1 GEMMs are 5 - 25 % SLOWER on it (ln1_qkv x3 60 -> 76 us, ln2_ffn1 x3 75 -> 80 us; a 3-stage
-// one-workgroup-a-CU variant 104 / 119 us): with K = 384 a tile is 6 dependent K-steps, the kernel is bound by the latency of that
-// chain and what hides it is the number of workgroups a CU holds, not the bytes or LDS reads per flop.  Kept as a tested variant.
-int& cfen_tune_gemm_big() {
-  static int v = 0;
-  return v;
-}
-int& cfen_tune_gemm_big_min_tiles() {   // the 192 x 128 tile is used when a launch has at least this many of them
-  static int v = 256;
-  return v;
-}
-int& cfen_tune_gemm_splitk_stages() {   // extra ring stages of the 96 x 128 split-K tile: 0 (two stages) or 3 (five stages, 140 KB)
-  static int v = 0;
-  return v;
-}
-int& cfen_tune_gemm_m128() {
-  static int v = 0;
-  return v;
-}
-int& cfen_tune_gemm_large() {
-  static int v = 4;
-  return v;
-}
-int& cfen_tune_gemm_mid() {   // more than 512 tiles of 96 x 32 and fewer than 1024 of 96 x 64 (the grouped GViT-2 decoder GEMMs, 3 x 512 tokens): kernel id as "gemm.small".
-  static int v = 2;            // Round 5, four forwards in flight, same box: 96 x 128 tiles (2) 2.059 / 2.060 ms per step, 96 x 64 (4) 2.094, 96 x 96 (3) 2.106, 96 x 32 on
-  return v;                    // 2 / 3 stages (5 / 15: rounds 2-4) 2.075-2.078 / 2.136 (profiles/r05_ab_gvit2_decoder_gemm_tiles.txt): a quarter of the weight bytes through the DMA path
-}
-int& cfen_tune_gemm_small() {
-  static int v = 15;   // 96 x 32 tiles, 3-stage ring: the few-token GViT GEMMs are latency bound (one K-step per memory round trip with 2 stages)
-  return v;
-}
-int& cfen_tune_gemm_kernel() {
-  static int v = -1;
   return v;
 }
 

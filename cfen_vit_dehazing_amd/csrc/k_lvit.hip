@@ -675,18 +675,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW / 4,
 
 }  // namespace
 
-int& cfen_tune_lvit_debug() {
-  static int v = 0;
-  return v;
-}
-
-int& cfen_tune_lvit_shape() {   // 2 (default): 16 waves x 1 token tile (four waves per SIMD, 128 registers, no spills: 2.858 -> 2.83 ms -- a wave issues a vector
-                                // instruction every ~10 cycles and two thirds of this kernel are vector-instruction bound); 0: 8 waves x 2 token tiles;
-                                // 1: 4 waves x 4 token tiles (one wave per SIMD, 512 registers)
-  static int v = 2;
-  return v;
-}
-
 bool cfen_lvit_window_supported(int dtype, int D, int heads, int S, int hidden) {
   return dtype == 1 && D == 96 && heads == 4 && S == 256 && hidden > 0 && hidden % 32 == 0;
 }

@@ -684,11 +684,6 @@ int launch_mlp(int ng, const MlpArgs* ap, hipStream_t s) {
 
 // D = 384 (LViT level 3, 8192 tokens per batch of 8) does not fill the chip with 128-token workgroups and its
 // 4.7 MB of weights per instance exceed what one CU can stream per token tile: the tiled GEMM path is faster there.
-int& cfen_tune_mlp_small_tiles() {
-  static int v = 10;
-  return v;
-}
-
 bool cfen_mlp_supported(int D, int H, int dtype) { return (D == 96 || D == 192) && H % (dtype == 1 ? 64 : 32) == 0; }
 
 int cfen_mlp_impl_g(int dtype, int ng, const MlpArgs* a, hipStream_t s) {

@@ -1222,23 +1222,6 @@ int launch_mlp3p(int ng, const Mlp3Args* ap, hipStream_t s) {
 
 }  // namespace
 
-int& cfen_tune_mlp3_pair() {   // D = 384 blocks on k_mlp3p (two waves per SIMD, the hidden dimension split over a wave pair): 0 = k_mlp3<24, ...>, 1 on (default, round 6: 134-150 us
-  static int v = 1;            // a launch against 152-172; +0.6-1.0 % on the headline step, level on the other two configurations), 2 on with stamps ("mlp3.pair")
-  return v;
-}
-int& cfen_tune_mlp3_tm192() {   // the D = 192 variant: 22 (default, round 5) = 2 token tiles a wave at 256 registers on a three-slot ring, two 78 KB workgroups a CU; 24 = the same
-  static int v = 22;            // on four slots (one workgroup a CU); 4 / 3 / 2 token tiles a wave on the six-slot ring of one 150 KB workgroup a CU (512 registers)
-  return v;
-}
-int& cfen_tune_mlp3_debug() {
-  static int v = 0;
-  return v;
-}
-int& cfen_tune_front3_debug() {
-  static int v = 0;
-  return v;
-}
-
 bool cfen_mlp3_supported(int dtype, int D, int H) { return dtype == 1 && (D == 384 || D == 192) && H % 32 == 0 && H > 0 && H <= (D == 384 ? 1536 : 768); }
 
 int cfen_mlp3_impl_g(int dtype, int ng, const Mlp3Args* ap, hipStream_t s) {

@@ -339,20 +339,6 @@ __global__ __launch_bounds__(768) void k_tail_fused(Grouped<TailArgs> ga, int nb
 
 }  // namespace
 
-int& cfen_tune_tail_balance() {   // work split between the wave groups ("tail.balance"): bit 0 = the 7x7's scale / tanh / store of all eight rows on the ConvTranspose waves.
-  static int v = 0;              // In-kernel stamps (tools/dbg_tail_stamps.py): per band the ConvTranspose waves are busy 3.05 us, the 3x3 waves 4.2, the 7x7 waves 3.45 -> with bit 0
-                                 // 3.3 / 3.8 / 3.45 and the launch 8 % shorter alone (265 against 287 us), but no faster with four forwards in flight (2.090-2.109 against 2.084-2.092 ms)
-  return v;
-}
-int& cfen_tune_tail_debug() {   // timing experiments (results invalid): 1 no ConvTranspose MFMAs, 2 no 3x3 MFMAs, 4 no 7x7 MFMAs, 8 no tanh, 16 no output stores, 32 no input fetch
-  static int v = 0;
-  return v;
-}
-int& cfen_tune_tail_segments() {   // vertical segments a strip is cut into ("tail.segments"): more workgroups against 5 fill / drain steps per segment.  Measured, batch 8:
-  static int v = 1;                // alone 4 segments are fastest (202 us against 235 for 2); with four forwards in flight fewer are: 2.043-2.048 ms per step on 4, 2.022-2.046 on 2, 2.023-2.035 on 1
-  return v;
-}
-
 bool cfen_tail_fused_supported(int dtype, int cs_in, int Cup_pad, int cs_up, int C3_pad, int Hin, int Win, int Cout7, int out_mode) {
   return dtype == 1 && cs_in % 8 == 0 && cs_in * 2 <= 64 && Cup_pad == 16 && cs_up == 16 && C3_pad == 16 && Hin % 4 == 0 && Win % 32 == 0 && Hin >= 8 &&
          Cout7 >= 1 && Cout7 <= 4 && (out_mode == 1 || out_mode == 3 || (out_mode == 2 && (Cout7 == 1 || Cout7 == 3)));

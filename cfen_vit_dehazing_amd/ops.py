@@ -4,6 +4,7 @@ Used by the parity tests and by anyone who wants one fused block instead of the 
 Every function launches on torch's current CUDA(=HIP) stream and raises CfenError on failure; there
 is no PyTorch fallback.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -19,18 +20,52 @@ def _cuda(*ts):
             raise ValueError("HIP operators need contiguous CUDA tensors")
 
 
-_TUNED = {}
-
-
 def tune(key, value):
-    """process-wide kernel-variant knob (cfen_tune); for benchmarks"""
+    """process-wide kernel-variant knob (cfen_tune; the table of knobs is csrc/cfen_tune_knobs.hpp); for benchmarks"""
     check(_lib.load().cfen_tune(key.encode(), int(value)), "tune")
-    _TUNED[key] = int(value)
 
 
-def tuned(key, default=None):
-    """what this process last set a knob to through tune() (None / `default` = never touched: the library's own default is in force)"""
-    return _TUNED.get(key, default)
+def _tune_query(key):
+    value, shipped = ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().cfen_tune_query(key.encode(), ctypes.byref(value), ctypes.byref(shipped)), "tune_query")
+    return value.value, shipped.value
+
+
+def tuned(key):
+    """the value of a knob now, read from the library (so a knob set through the C ABI directly is seen too)"""
+    return _tune_query(key)[0]
+
+
+def tune_keys():
+    """every knob's key, in the order of the library's table"""
+    lib = _lib.load()
+    keys = []
+    while True:
+        k = lib.cfen_tune_key(len(keys))
+        if k is None:
+            return keys
+        keys.append(k.decode())
+
+
+def tune_not_shipped():
+    """{key: (value, shipped default)} of the knobs that are not at their shipped default"""
+    return {k: vs for k, vs in ((k, _tune_query(k)) for k in tune_keys()) if vs[0] != vs[1]}
+
+
+@contextlib.contextmanager
+def tuning(knobs):
+    """with ops.tuning({key: value, ...}): sets the knobs in order, and puts the values they had back in reverse order on the way out
+    (also when the body raises, and for the knobs already set when a later one is refused)"""
+    undo = []
+    try:
+        for key, value in knobs.items():
+            before = tuned(key)
+            tune(key, value)
+            undo.append((key, before))
+        yield
+    finally:
+        for key, before in reversed(undo):
+            tune(key, before)
 
 
 def gemm_nt(x, w, bias=None, residual=None, pos=None, relu=False, out=None):

@@ -34,39 +34,18 @@ extern "C" {
 
 int cfen_abi_version(void);
 const char* cfen_last_error(void);
-/* Process-wide tuning knobs for benchmarking kernel variants (tools/bench_gemm.py); the defaults are what ships.
- *   "gemm.kernel": -1 choose by shape (default), 0 register-staged k_gemm_nt, 1 k_gemm_skinny, 2..5 LDS-DMA k_gemm_dma with a
- *                  96 x 128 / 96 / 64 / 32 (features x tokens) tile (1..5 need K * element size to be a multiple of 128 bytes)
- *   "embed.lds": bit 2 (default 6): the LDS-DMA-ring front half k_embed_qkv2; else k_embed_qkv stages its weights through LDS for D = 96 (bit 0) / D = 192 (bit 1)
- *   "gemm.splitk": 0 (default, round 4) / 1: K-heavy few-token GEMMs inside the net run split-K with the in-launch reduction (scratch from the workspace).
- *                  (off by default because the unsplit launches are faster with several forwards in flight; bitwise right there too)
- *   "mlp.small_tiles": fused-MLP kernel variant: 0..4 the register-staged k_mlp tilings, >= 10 (default 10) the LDS-DMA k_mlp2 (tens digit:
- *                  D = 96 variant, ones digit: D = 192 variant, see k_mlp.hip);  "net.fused_front_max_dim": largest LViT embedding dim that uses k_embed_qkv
- *   "net.skip_classes": bit mask of kernel classes the net does NOT launch (what-if timing only, outputs invalid)
- *   "net.attn_head_major": 1 (default) LViT levels with a fused front half pass qkv to attention per (window, head); 0 row-major [M][3D]
- *   "net.ln_fold": 1 (default) LN1 / LN2 of GViT and LViT level 3 are folded into the qkv / ffn1 GEMMs (cfen_gemm_ln), 0 separate LayerNorm launches
- *   "net.embed_gather": 1 (default) the LViT embedding GEMM gathers its patch tokens from the map, 0 separate patchify launch
- *                  (read when a forward is enqueued or a graph is built)
- *   "gemm.large" / "gemm.small": the k_gemm_dma tile (2..5) the shape rule uses for problems with >= / < 1024 tiles of 96 x 64
- *   "gemm.mid": the k_gemm_dma tile for launches of more than 512 tiles of 96 x 32 and fewer than 1024 of 96 x 64 (the grouped GViT-2 decoder GEMMs): 2 (default,
- *                  round 5) 96 x 128, 5 / 15 the 96 x 32 tiles of rounds 2-4 on 2 / 3 stages
- *   "net.tail_fused": the decoders' output tails (us_conv_d01* ConvTranspose, 3x3, reflect-pad 7x7 + tanh): 2 (default, round 5) ONE launch (k_tail_fused, both
- *                  intermediate maps in LDS), 1 ConvTranspose + 3x3 fused (k_up_conv3_fused) + the 7x7, 0 three launches -- bitwise equal;  "tail.segments" (default 1):
- *                  vertical segments a 64-column strip of k_tail_fused is cut into;  "tail.debug": timing experiments (results invalid)
- *   what-if probes (timing only, results invalid): "net.skip_from" / "net.skip_to" leave out the launches of that number range of a forward; "net.extra_launches" adds
- *                  that many one-workgroup launches in front of every ViT block; "net.gvit_dummy_wgs" / "_us" / "_levels" replace GViT blocks by a launch that only holds CUs
- *   "net.gvit_stream": GViT level 1 (embedding dim 384) on the LViT-3 stream kernels: 0 never, 1 in the single-lane plan only, 2 (default, round 5) on every
- *                  plan -- which kernels produce the outputs does not depend on the launch plan or on profiling
- *   "gvit.max_concurrent": 1 (default) .. 8: forwards of the persistent-chain plan ("net.gvit_chain") that may be in flight at once; the teams of all of them
- *                  must be resident together (grid barriers), so the host caps a team at 256 / (groups x this) CUs
- *   "mlp3.pair" (default 1, round 6): the D = 384 block (projection + LayerNorm + both stages) on k_mlp3p -- wave pairs, two waves per SIMD; 0 = k_mlp3<24, ...> (one wave per SIMD;
- *       results equal to 1-2 fp16 ulp: the LayerNorm sums associate over the pair); 2 = k_mlp3p's stamped timing build (prints to stderr, synchronises)
- *   "net.stream_mlp192" (default 1) / "mlp3.tm192" (default 22): LViT level 2's proj + MLP block on k_mlp3: 22 = two 4-wave 78 KB workgroups a CU on a three-slot ring
- *                  (256 registers); 24 four slots; 28 / 29 one 8-wave workgroup a CU; 2 / 3 / 4 token tiles a wave on one 150 KB workgroup a CU; net.stream_mlp192 = 0: k_mlp2
- *   "embed.stages": 2 .. 5 ring stages of k_embed_qkv2 at D = 192 (default 4)
- *   "lvit.shape": k_lvit_window's workgroup shape / schedule: 2 (default) 16 waves x 1 token tile, 0 8 x 2, 1 4 x 4, 3 denominator by MFMA, 4 / 5 the 16 x 1 / 8 x 2
- *                  shapes with hand-issued K / V fragment reads, 6 64-row front chunks (round 5: bitwise equal, not faster); 8 / 9 timing experiments without the softmax (results invalid) */
+/* Process-wide tuning knobs for benchmarking kernel variants ("gemm.kernel", "net.tail_fused", ...); the defaults are what ships.
+ * Every key, its shipped default, the values it takes and what they select are ONE table: cfen_vit_dehazing_amd/csrc/cfen_tune_knobs.hpp
+ * (plain text rows with a comment each; ship it beside this header as the knobs' documentation -- INTEGRATION.md).  At run time the library
+ * itself answers which keys exist and what their defaults are (cfen_tune_key, cfen_tune_query), and a refusal names the values a knob takes.
+ * The knobs are read when a forward is enqueued or a graph is built.  None of the three calls touches the GPU; none is thread safe.
+ *   cfen_tune        sets a knob.  Unknown key, or a value the knob's rule refuses: CFEN_ERR_ARG, nothing changes.  Some rules store a
+ *                    normalised value (on / off knobs store value != 0, "embed.lds" stores value & 7).
+ *   cfen_tune_query  reads a knob's current value and its shipped default (either pointer may be NULL); CFEN_ERR_ARG for an unknown key.
+ *   cfen_tune_key    the key of knob number `index` (0, 1, ...), NULL past the last one. */
 int cfen_tune(const char* key, int value);
+int cfen_tune_query(const char* key, int* value, int* shipped_default);
+const char* cfen_tune_key(int index);
 
 /* ---- whole generator: replaces define_G (v3:93-100) + dec_ipt.forward (v3:392-1020) ------------- */
 typedef struct cfen_net cfen_net;

@@ -4,11 +4,25 @@ import os
 import zlib
 
 import numpy as np
+import pytest
 import torch
 
 from cfen_vit_dehazing_amd.config import NetConfig
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(autouse=True)
+def knobs_at_shipped_defaults():
+    """The tuning knobs are process-wide: a test that leaves one changed changes what every later test of the process runs.  Imported by the GPU
+    test modules (autouse there): after every test, every knob must be at its shipped default again -- tests change knobs inside `with ops.tuning`.
+    Offenders are put back before the assertion, so one slip fails one test."""
+    yield
+    from cfen_vit_dehazing_amd import ops
+    left = ops.tune_not_shipped()
+    for key, (_, shipped) in left.items():
+        ops.tune(key, shipped)
+    assert not left, "knobs left off their shipped default {key: (value, default)}: %r" % left
 
 
 def load_net_fixture(name):

@@ -69,6 +69,97 @@ def test_tuning_knobs_validate_without_a_gpu():
         assert lib.cfen_tune(key, val) == 0, key       # (the shipped defaults: the knobs are process-wide)
 
 
+
+# The 61 knobs of the table (csrc/cfen_tune_knobs.hpp), as the strcmp ladder of cfen_tune() spelled them before the table existed.
+KNOB_KEYS = """gemm.kernel gemm.large gemm.small gemm.mid gemm.big convT.tpw conv7.tpw conv.wlds conv.wlds_maxlog gemm.big_min_tiles embed.lds embed.stages
+    mlp3.tm192 embed.defer_refill gemm.defer_refill lvit.debug front3.debug mlp3.pair mlp3.debug gemm.m128 gemm.splitk_stages gemm.splitk_release gemm.splitk
+    net.ln_fold net.fused_front_max_dim net.skip_classes mlp.small_tiles lvit.shape net.lvit_window net.fold_in_gemm net.attn_head_major dcn.tps gemm.nt dcn.tile
+    attn.hm_pair net.head_fused net.stream_front net.stream_mlp192 net.stream_mlp net.gvit_dummy_wgs net.gvit_dummy_us net.skip_from net.skip_to
+    net.extra_launches net.gvit_dummy_levels net.gvit_dummy_stream gvit.team net.gvit_stream gvit.max_concurrent net.tail_fused tail.balance tail.debug
+    tail.segments net.up_fused net.zero_memset net.keep_stages net.resblock_fused net.head5 gvit.debug net.gvit_chain net.embed_gather""".split()
+# The defaults the GPU tests spelled out in their `finally:` blocks for six rounds (they restore through ops.tuning now and know none): pinned here so
+# the table cannot drift silently from them.  "net.resblock_fused" is the one those tests had wrong (they restored 1; the library ships 0).
+PINNED_DEFAULTS = {"gemm.splitk": 0, "gemm.splitk_release": 1, "gemm.kernel": -1, "gemm.big": 0, "gemm.big_min_tiles": 256, "attn.hm_pair": 0, "embed.lds": 6,
+                   "embed.stages": 4, "conv.wlds": 2, "conv7.tpw": 4, "convT.tpw": 2, "mlp3.tm192": 22, "mlp3.pair": 1, "lvit.shape": 2, "net.head_fused": 0,
+                   "net.head5": 1, "net.tail_fused": 2, "net.keep_stages": 0, "tail.segments": 1, "net.up_fused": 0, "net.gvit_stream": 2,
+                   "gvit.max_concurrent": 1, "dcn.tile": 1, "net.resblock_fused": 0}
+
+
+def _query(lib, key):
+    value, shipped = ctypes.c_int(-12345), ctypes.c_int(-12345)
+    assert lib.cfen_tune_query(key.encode(), ctypes.byref(value), ctypes.byref(shipped)) == 0, key
+    return value.value, shipped.value
+
+
+def test_knob_enumeration_is_the_61_keys():
+    from cfen_vit_dehazing_amd import _lib, ops
+    lib = _lib.load()
+    keys = ops.tune_keys()
+    assert len(keys) == 61 and len(set(keys)) == 61
+    assert sorted(keys) == sorted(KNOB_KEYS)
+    assert lib.cfen_tune_key(61) is None and lib.cfen_tune_key(-1) is None and lib.cfen_tune_key(1 << 30) is None
+    assert lib.cfen_tune_query(b"no.such.knob", None, None) == -1 and b"unknown key" in lib.cfen_last_error()
+    assert lib.cfen_tune_query(b"gemm.kernel", None, None) == 0            # either pointer may be NULL
+
+
+def test_knobs_of_a_fresh_process_are_at_their_shipped_defaults():
+    """in an interpreter of its own, so that no test that ran before in this process can matter"""
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from cfen_vit_dehazing_amd import ops\n"
+            "keys = ops.tune_keys()\n"
+            "assert len(keys) == 61 and not ops.tune_not_shipped(), ops.tune_not_shipped()\n"
+            "print('fresh ok', len(keys))\n" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "fresh ok 61" in r.stdout, r.stdout + r.stderr
+
+
+def test_every_knob_takes_its_own_default_and_pinned_defaults_hold():
+    from cfen_vit_dehazing_amd import _lib
+    lib = _lib.load()
+    before = {k: _query(lib, k) for k in KNOB_KEYS}
+    for k, (_, shipped) in before.items():
+        assert lib.cfen_tune(k.encode(), shipped) == 0, (k, shipped, lib.cfen_last_error())
+        assert _query(lib, k) == (shipped, shipped), k
+    for k, (value, _) in before.items():          # (put back whatever an earlier test of this process left: this test changes nothing for good)
+        assert lib.cfen_tune(k.encode(), value) == 0
+    assert {k: _query(lib, k) for k in KNOB_KEYS} == before
+    assert {k: before[k][1] for k in PINNED_DEFAULTS} == PINNED_DEFAULTS
+
+
+def test_knob_values_are_normalised_and_a_refused_value_changes_nothing():
+    from cfen_vit_dehazing_amd import _lib, ops
+    lib = _lib.load()
+    with ops.tuning({"net.head5": 7, "embed.lds": 15, "net.keep_stages": -3}):
+        assert ops.tuned("net.head5") == 1 and ops.tuned("embed.lds") == 7 and ops.tuned("net.keep_stages") == 1
+    for key, refused in (("gemm.kernel", 26), ("gemm.kernel", -2), ("gemm.mid", 7), ("gemm.big", 1), ("gemm.m128", 5), ("gemm.splitk_stages", 1), ("mlp3.tm192", 23),
+                         ("embed.stages", 6), ("net.stream_front", 3), ("net.gvit_stream", -1), ("tail.segments", 65), ("gvit.team", 86), ("gvit.max_concurrent", 9),
+                         ("convT.tpw", 0), ("conv7.tpw", 0), ("gemm.big_min_tiles", 0), ("conv.wlds", -1), ("conv.wlds_maxlog", -1)):
+        before = ops.tuned(key)
+        assert lib.cfen_tune(key.encode(), refused) == -1, (key, refused)
+        assert key.encode() in lib.cfen_last_error() and ops.tuned(key) == before, key
+
+
+def test_tuning_context_restores_previous_values():
+    from cfen_vit_dehazing_amd import ops
+    from cfen_vit_dehazing_amd._lib import CfenError
+    start = {k: ops.tuned(k) for k in KNOB_KEYS}
+    with ops.tuning({"tail.segments": 4}):
+        with ops.tuning({"tail.segments": 8, "net.tail_fused": 0}):          # nests: the inner block gives back the OUTER block's value, not the default
+            assert (ops.tuned("tail.segments"), ops.tuned("net.tail_fused")) == (8, 0)
+        assert (ops.tuned("tail.segments"), ops.tuned("net.tail_fused")) == (4, start["net.tail_fused"])
+        with pytest.raises(ZeroDivisionError):                                 # an exception in the body
+            with ops.tuning({"tail.segments": 2, "conv.wlds": 0}):
+                1 / 0
+        assert (ops.tuned("tail.segments"), ops.tuned("conv.wlds")) == (4, start["conv.wlds"])
+        with pytest.raises(CfenError, match="gemm.big"):                       # a refused key: the sets already made are undone, the body never runs
+            with ops.tuning({"tail.segments": 16, "gemm.big": 1, "conv.wlds": 0}):
+                raise AssertionError("the body must not run")
+        assert (ops.tuned("tail.segments"), ops.tuned("conv.wlds")) == (4, start["conv.wlds"])
+    assert {k: ops.tuned(k) for k in KNOB_KEYS} == start
+
+
 def _pack_and_register(cfg, dtype, wtile):
     import torch
     from cfen_vit_dehazing_amd import _lib

@@ -7,6 +7,7 @@ import torch.nn.functional as F
 
 import dcn_oracle
 from cfen_vit_dehazing_amd import dcn
+from helpers import knobs_at_shipped_defaults  # noqa: F401  (autouse: every knob is back at its shipped default after each test)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -55,11 +56,10 @@ def test_lean_kernel_and_round2_kernel_agree(C, dg):
     off = rnd((2, dg * 18, H, H), 23, 3.0).half().to(DEV)
     mask = torch.sigmoid(rnd((2, dg * 9, H, H), 24)).half().to(DEV)
     bias = rnd((C,), 25).half().to(DEV)
-    try:
-        got = [(dcn.deform_conv(x, off, w, 1, 1, 1, 1, dg), dcn.modulated_deform_conv(x, off, mask, w, bias, 1, 1, 1, 1, dg))
-               for t in (1, 0) if ops.tune("dcn.tile", t) is None]
-    finally:
-        ops.tune("dcn.tile", 1)
+    got = []
+    for t in (1, 0):
+        with ops.tuning({"dcn.tile": t}):
+            got.append((dcn.deform_conv(x, off, w, 1, 1, 1, 1, dg), dcn.modulated_deform_conv(x, off, mask, w, bias, 1, 1, 1, 1, dg)))
     for a, b in zip(got[0], got[1]):
         assert float((a.float() - b.float()).abs().max()) <= 8e-3
 

@@ -15,13 +15,13 @@ from cfen_vit_dehazing_amd.hipnet import dec_ipt
 from cfen_vit_dehazing_amd.manifest import generate_state_dict, synthetic_input
 from cfen_vit_dehazing_amd import ops
 from helpers import load_net_fixture, check_outputs, check_stages, weight_mode, sample_idx
+from helpers import knobs_at_shipped_defaults  # noqa: F401  (autouse: every knob is back at its shipped default after each test)
 
 pytestmark = pytest.mark.gpu
 
 # max-abs bar of the fp16 path on outputs in (-1, 1) with the seeded weights: measured 8.7e-4 .. 9.9e-4 at 512 x 512 in every record of rounds 1-4; the bar sits
 # 5x above that (it was 3e-2: a kernel regression costing a factor 10 in accuracy passed every gate -- VERDICT r04)
 FP16_BAR = 5e-3
-TAIL_FUSED_DEFAULT = 2   # "net.tail_fused" of the shipped library (restored by tests that change it)
 
 
 _SD_CACHE = {}
@@ -238,16 +238,13 @@ def test_split_k_and_grouping_knobs_do_not_change_results():
     cfg = NetConfig(24, 4, patch_size=32, load_size=256)
     x = synthetic_input(1, cfg).to("cuda:0")
     outs = {}
-    try:
-        for k in (1, 0):
-            ops.tune("gemm.splitk", k)
+    for k in (1, 0):
+        with ops.tuning({"gemm.splitk": k}):
             net = make_net(cfg, "fp16")
             a = [o.clone() for o in net(x)]
             b = [o.clone() for o in net(x)]
             assert all(torch.equal(p, q) for p, q in zip(a, b))
             outs[k] = a
-    finally:
-        ops.tune("gemm.splitk", 0)          # the shipped default (round 4)
     for p, q in zip(outs[0], outs[1]):
         assert float((p - q).abs().max()) < 5e-3
 
@@ -424,19 +421,14 @@ def test_fused_head_equals_the_three_convolutions_bitwise(size):
     cfg = NetConfig(24, 4, patch_size=ps, load_size=ls)
     x = synthetic_input(2, cfg).to("cuda:0")
     res = {}
-    try:
-        ops.tune("net.head5", 0)                 # (round 4's k_head5 sums its products in another order: the three round-3 launches are the twin here)
-        ops.tune("net.resblock_fused", 0)
+    # (round 4's k_head5 sums its products in another order: the three round-3 launches are the twin here)
+    with ops.tuning({"net.head5": 0, "net.resblock_fused": 0}):
         for k in (1, 0):
-            ops.tune("net.head_fused", k)
-            net = make_net(cfg, "fp16")
-            outs = [o.clone() for o in net(x)]
-            res[k] = (net.stage("head").clone(), outs)
-            del net
-    finally:
-        ops.tune("net.head_fused", 0)
-        ops.tune("net.head5", 1)
-        ops.tune("net.resblock_fused", 1)
+            with ops.tuning({"net.head_fused": k}):
+                net = make_net(cfg, "fp16")
+                outs = [o.clone() for o in net(x)]
+                res[k] = (net.stage("head").clone(), outs)
+                del net
     assert torch.equal(res[1][0], res[0][0])
     for a, b in zip(res[1][1], res[0][1]):
         assert torch.equal(a, b)
@@ -454,19 +446,14 @@ def test_head_from_input_and_fused_resblock_against_the_unfused_launches(size):
     n = cfg.image_size
     img = torch.randint(0, 256, (2, n, n, 3), generator=torch.Generator().manual_seed(5), dtype=torch.uint8).to("cuda:0")
     res = {}
-    try:
-        for h5, rb in ((0, 0), (1, 0), (0, 1), (1, 1)):
-            ops.tune("net.head5", h5)
-            ops.tune("net.resblock_fused", rb)
+    for h5, rb in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        with ops.tuning({"net.head5": h5, "net.resblock_fused": rb}):
             net = make_net(cfg, "fp16")
             outs = [o.clone() for o in net(x)]
             head = net.stage("head").clone()
             outs8 = [o.clone() for o in net(img)]
             res[(h5, rb)] = (head, outs, outs8)
             del net
-    finally:
-        ops.tune("net.head5", 1)
-        ops.tune("net.resblock_fused", 1)
     # the fused ResBlock is bitwise the two launches (same accumulation order, same fp16 rounding of the hidden map) ...
     for h5 in (0, 1):
         a, b = res[(h5, 1)], res[(h5, 0)]
@@ -495,14 +482,11 @@ def test_fused_tail_equals_the_separate_launches_bitwise(size, batch):
     cfg = NetConfig(24, 4, patch_size=ps, load_size=ls)
     x = synthetic_input(batch, cfg).to("cuda:0")
     res = {}
-    try:
-        configs = ((0, 0, 4), (1, 1, 4), (1, 0, 4), (2, 0, 4), (2, 0, 1), (2, 0, 2), (2, 0, 8))
-        if ls >= 256:       # 512 x 512 and 1024 x 1024: the separate launches, the round-4 pair with its stage maps, the shipped shape and one other segmentation
-            configs = ((0, 0, 4), (1, 1, 4), (2, 0, 1), (2, 0, 4)) if ls == 256 else ((0, 0, 4), (1, 1, 4), (2, 0, 1))
-        for fused, keep, seg in configs:
-            ops.tune("net.tail_fused", fused)
-            ops.tune("net.keep_stages", keep)
-            ops.tune("tail.segments", seg)
+    configs = ((0, 0, 4), (1, 1, 4), (1, 0, 4), (2, 0, 4), (2, 0, 1), (2, 0, 2), (2, 0, 8))
+    if ls >= 256:       # 512 x 512 and 1024 x 1024: the separate launches, the round-4 pair with its stage maps, the shipped shape and one other segmentation
+        configs = ((0, 0, 4), (1, 1, 4), (2, 0, 1), (2, 0, 4)) if ls == 256 else ((0, 0, 4), (1, 1, 4), (2, 0, 1))
+    for fused, keep, seg in configs:
+        with ops.tuning({"net.tail_fused": fused, "net.keep_stages": keep, "tail.segments": seg}):
             net = make_net(cfg, "fp16")
             outs = [o.clone() for o in net(x)]
             if fused and not keep:
@@ -521,10 +505,6 @@ def test_fused_tail_equals_the_separate_launches_bitwise(size, batch):
             net.output_u8 = False
             res[(fused, keep, seg)] = (outs, st, u8)
             del net
-    finally:
-        ops.tune("net.tail_fused", TAIL_FUSED_DEFAULT)
-        ops.tune("net.keep_stages", 0)
-        ops.tune("tail.segments", 1)
     ref = res[(0, 0, 4)]
     for key, got in res.items():
         for a, b in zip(got[0], ref[0]):
@@ -548,9 +528,8 @@ def test_gvit_upsampling_inside_the_fuse_conv_equals_the_upsample_launch(size, b
     x = synthetic_input(batch, cfg).to("cuda:0")
     names = ["lgcat_conv_e01", "lgcat_conv_e02", "lgcat_conv_e03", "lgcat_conv_d03r", "lgcat_conv_d02s", "lgcat_conv_d01d"]
     res = {}
-    try:
-        for fused in (0, 1):
-            ops.tune("net.up_fused", fused)
+    for fused in (0, 1):
+        with ops.tuning({"net.up_fused": fused}):
             net = make_net(cfg, "fp16")
             net(x)                                   # first forward initialises nothing here (trained ActNorm), second is the measured plan
             outs = [o.clone() for o in net(x)]
@@ -570,8 +549,6 @@ def test_gvit_upsampling_inside_the_fuse_conv_equals_the_upsample_launch(size, b
                 assert torch.equal(a, b)
             res[fused] = (outs, st)
             del net
-    finally:
-        ops.tune("net.up_fused", 0)
     # the same interpolation in two kernels: fp32 sums the compiler contracts differently, then one rounding to fp16 -- last-bit differences of the GViT half of
     # the fuse conv's input (forcing separate multiplies and adds in both made the plans bitwise equal and k_upsample4 20 % slower: not worth it for a variant)
     for k in names:
@@ -591,8 +568,7 @@ def test_gvit_persistent_chain_plan_agrees_with_the_launch_per_gemm_plan():
     cfg = NetConfig(24, 4, patch_size=32, load_size=256)
     x = synthetic_input(8, cfg).to("cuda:0")
     stages = ["globalvit_encoder_01", "globalvit_encoder_02", "globalvit_encoder_03", "globalvit_decoder_03r", "globalvit_decoder_02s", "globalvit_decoder_01d"]
-    ops.tune("net.keep_stages", 1)          # the GViT maps are stored at full resolution (default: x4 bilinear inside the fuse convs)
-    try:
+    with ops.tuning({"net.keep_stages": 1}):          # the GViT maps are stored at full resolution (default: x4 bilinear inside the fuse convs)
         base = make_net(cfg, "fp16")
         want = [o.clone() for o in base(x)]
         wst = {k: base.stage(k).clone() for k in stages}
@@ -608,8 +584,6 @@ def test_gvit_persistent_chain_plan_agrees_with_the_launch_per_gemm_plan():
         for k in stages:
             d = float((net.stage(k) - wst[k]).abs().max())
             assert d <= 3e-2 * max(1.0, float(wst[k].abs().max())), (k, d)
-    finally:
-        ops.tune("net.keep_stages", 0)
     for a, b in zip(got, want):
         assert float((a - b).abs().max()) <= 2e-2
     gid, gouts = net.capture(x)
@@ -637,26 +611,24 @@ def test_three_forwards_in_flight_on_replica_plans_match_single_forwards_bitwise
     from cfen_vit_dehazing_amd import ops
     from cfen_vit_dehazing_amd.parallel import split_slab
     cfg = NetConfig(24, 4, patch_size=32, load_size=256)
-    ops.tune("gemm.splitk", int(splitk == 1))
     if splitk == 2:
         os.environ["CFEN_GVIT_CHAIN"] = "1"
     try:
-        net = make_net(cfg, "fp16")
-        assert bool(net.gvit_chain) == (splitk == 2)
-        if splitk == 2:
-            # the chains' grid barriers need every team of every forward in flight resident at once: without the cap a second replica is refused
-            net.replica = 1
-            with pytest.raises(Exception, match="gvit.max_concurrent"):
-                net(synthetic_input(8, cfg).to("cuda:0"))
-            net.replica = 0
-            ops.tune("gvit.max_concurrent", 3)
-        _three_in_flight(net, cfg, split_slab)
-        if splitk == 2:
-            assert net.chain_errors() == [0, 0, 0]
+        with ops.tuning({"gemm.splitk": int(splitk == 1)}):
+            net = make_net(cfg, "fp16")
+            assert bool(net.gvit_chain) == (splitk == 2)
+            if splitk == 2:
+                # the chains' grid barriers need every team of every forward in flight resident at once: without the cap a second replica is refused
+                net.replica = 1
+                with pytest.raises(Exception, match="gvit.max_concurrent"):
+                    net(synthetic_input(8, cfg).to("cuda:0"))
+                net.replica = 0
+            with ops.tuning({"gvit.max_concurrent": 3} if splitk == 2 else {}):
+                _three_in_flight(net, cfg, split_slab)
+                if splitk == 2:
+                    assert net.chain_errors() == [0, 0, 0]
     finally:
         os.environ.pop("CFEN_GVIT_CHAIN", None)
-        ops.tune("gemm.splitk", 0)
-        ops.tune("gvit.max_concurrent", 1)
 
 
 def _three_in_flight(net, cfg, split_slab):
@@ -698,10 +670,8 @@ def test_two_lane_plan_equals_serial_plan_bitwise_full_size():
     cfg = NetConfig(24, 4, patch_size=32, load_size=256)
     x = synthetic_input(2, cfg).to("cuda:0")
     res = {}
-    try:
-        for mode in (0, 2):
-            ops.tune("net.gvit_stream", mode)
-            ops.tune("net.keep_stages", 1)
+    for mode in (0, 2):
+        with ops.tuning({"net.gvit_stream": mode, "net.keep_stages": 1}):
             net = make_net(cfg, "fp16")
             net.serial_plan = False
             two = [o.clone() for o in net(x)]
@@ -718,9 +688,6 @@ def test_two_lane_plan_equals_serial_plan_bitwise_full_size():
                 assert torch.equal(a, b) and torch.equal(a, c)
             res[mode] = (two, st)
             del net
-    finally:
-        ops.tune("net.gvit_stream", 2)
-        ops.tune("net.keep_stages", 0)
     st0, st2 = res[0][1], res[2][1]
     assert float((st0 - st2).abs().max()) <= 3e-2 * max(1.0, float(st0.abs().max()))
     for a, b in zip(res[0][0], res[2][0]):
@@ -800,12 +767,9 @@ def test_reference_init_weights_fp16_psnr_ssim_full512():
         sd[k + ".weight"], sd[k + ".bias"] = torch.from_numpy(z["actnorm_w/" + k]), torch.from_numpy(z["actnorm_b/" + k])
         sd[k + ".initialized"] = torch.tensor(1)
     net2 = make_net(cfg, "fp16", sd=sd)
-    ops.tune("net.keep_stages", 1)
-    try:
+    with ops.tuning({"net.keep_stages": 1}):
         w2 = _fp16_vs_fixture(z, net2(x), x, REFINIT_FP16_BAR)
         st = gpu_stages(net2, z)
-    finally:
-        ops.tune("net.keep_stages", 0)
     rows = []
     for n, t in st.items():
         smp = t.float().cpu().flatten()[sample_idx(n, t.numel())].numpy()
@@ -842,12 +806,9 @@ def test_fp16_outputs_written_by_the_fused_tail_equal_the_rounded_float_outputs(
     # ... and where the plan falls back to the separate tail launches
     net2 = make_net(cfg, "fp16")
     net2.output_f16 = True
-    ops.tune("net.tail_fused", 1)
-    try:
+    with ops.tuning({"net.tail_fused": 1}):
         with pytest.raises(Exception):
             net2(x)
-    finally:
-        ops.tune("net.tail_fused", TAIL_FUSED_DEFAULT)
 
 
 def test_uint8_input_equals_host_normalised_input():

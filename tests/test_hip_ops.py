@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 import cfen_oracle
 from cfen_vit_dehazing_amd import ops, packing
+from helpers import knobs_at_shipped_defaults  # noqa: F401  (autouse: every knob is back at its shipped default after each test)
 
 pytestmark = pytest.mark.gpu
 DTYPES = [torch.float32, torch.float16]
@@ -136,8 +137,7 @@ def test_gemm_split_k_is_bit_reproducible_with_concurrent_lanes(release):
     stream keeps the memory system busy; every result must equal the first one bit for bit and the arrival counters must end at zero.  release = 1: the agent-scope
     release fence in every slice (default, the memory model's recipe); 0: round 3's write-through stores + drain."""
     d = dev()
-    ops.tune("gemm.splitk_release", release)
-    try:
+    with ops.tuning({"gemm.splitk_release": release}):
         lanes = []
         for k, (M, N, K, nsplit) in enumerate([(128, 1536, 6144, 8), (128, 1536, 1536, 4)]):
             x, w = rnd((M, K), 10 + k, torch.float16).to(d), rnd((N, K), 20 + k, torch.float16, 1 / math.sqrt(K)).to(d)
@@ -157,8 +157,6 @@ def test_gemm_split_k_is_bit_reproducible_with_concurrent_lanes(release):
         for x, w, nsplit, scratch, first, s, bad in lanes:
             assert int(bad) == 0
             assert int(scratch[:4096].view(torch.int32).abs().sum()) == 0
-    finally:
-        ops.tune("gemm.splitk_release", 1)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -171,8 +169,7 @@ def test_gemm_big_tile(dtype, kernel, M, N, K):
     bias, res, pos = rnd((N,), 3, torch.float32), rnd((M, N), 4, dtype), rnd((16, N), 5, dtype)
     ref = x.double() @ w.double().t()
     d = dev()
-    ops.tune("gemm.kernel", kernel)
-    try:
+    with ops.tuning({"gemm.kernel": kernel}):
         close(ops.gemm_nt(x.to(d), w.to(d)), ref, tol(dtype, 4), "plain")
         want = torch.relu(ref + bias.double()) + res.double() + pos.double()[torch.arange(M) % 16]
         close(ops.gemm_nt(x.to(d), w.to(d), bias=bias.to(d), residual=res.to(d), pos=pos.to(d), relu=True), want, tol(dtype, 8), "bias+relu+res+pos")
@@ -180,8 +177,6 @@ def test_gemm_big_tile(dtype, kernel, M, N, K):
         ops.gemm_nt(x.to(d), w.to(d), residual=r, out=r)
         close(r, ref + res.double(), tol(dtype, 8), "in-place residual")
         base = ops.gemm_nt(x.to(d), w.to(d), bias=bias.to(d), relu=True)
-    finally:
-        ops.tune("gemm.kernel", -1)
     other = ops.gemm_nt(x.to(d), w.to(d), bias=bias.to(d), relu=True)          # the shape rule's own choice: same sums, same order of K
     assert torch.equal(base, other) or float((base.float() - other.float()).abs().max()) <= tol(dtype, 4)
 
@@ -195,14 +190,9 @@ def test_gemm_big_tile_with_layernorm_folded(dtype):
     g, b, bias = 1 + 0.1 * rnd((D,), 3, torch.float32), 0.1 * rnd((D,), 4, torch.float32), rnd((N,), 5, torch.float32)
     want = (cfen_oracle.layer_norm(x.double(), g.double(), b.double()) @ w.double().t() + bias.double()).relu()
     f = ln_folded(None, g, b, bias, "l", dtype, w)
-    ops.tune("gemm.big_min_tiles", 1)
-    try:
-        ops.tune("gemm.big", 6)
+    with ops.tuning({"gemm.big_min_tiles": 1, "gemm.big": 6}):
         got = ops.gemm_ln(x.to(dev()), f["l.wl"].to(dev()), f["l.s"].to(dev()), f["l.bl"].to(dev()), relu=True)
         close(got, want, tol(dtype, 8))
-    finally:
-        ops.tune("gemm.big", 0)
-        ops.tune("gemm.big_min_tiles", 256)
 
 
 def attn_ref(qkv, nseq, S, heads):
@@ -238,11 +228,9 @@ def test_attention_head_major_layout(nseq, S, heads):
     got = ops.attention_head_major(to_head_major(qkv, nseq, S, heads).to(dev()), nseq, S, heads)
     close(got, attn_ref(qkv, nseq, S, heads), tol(torch.float16, 3))
     if S in (256, 1024):   # S = 1024: the 8-wave form of the long-window kernel (key blocks of 256) beside the default 16-wave one (blocks of 128);
-        try:               # S = 256: the long-window kernel (two query tiles per K / V fragment) instead of k_attention_hm
-            ops.tune("attn.hm_pair", 2 if S == 1024 else 1)
+        # S = 256: the long-window kernel (two query tiles per K / V fragment) instead of k_attention_hm
+        with ops.tuning({"attn.hm_pair": 2 if S == 1024 else 1}):
             got8 = ops.attention_head_major(to_head_major(qkv, nseq, S, heads).to(dev()), nseq, S, heads)
-        finally:
-            ops.tune("attn.hm_pair", 0)
         close(got8, attn_ref(qkv, nseq, S, heads), tol(torch.float16, 3))
 
 
@@ -374,43 +362,31 @@ def test_embed_qkv_fused_front(dtype, C, H, W, ws):
     wq = rnd((3 * D, D), 7, dtype, 1 / math.sqrt(D))
     perm = packing.kperm32(D) if dtype == torch.float16 else torch.arange(D)
     res = []
-    try:
-        for lds in (0, 3, 4):               # weights straight from L2 / staged through LDS / LDS-DMA ring (fp16 only): same arithmetic
-            ops.tune("embed.lds", lds)
+    for lds in (0, 3, 4):               # weights straight from L2 / staged through LDS / LDS-DMA ring (fp16 only): same arithmetic
+        with ops.tuning({"embed.lds": lds}):
             res.append(ops.embed_qkv(fmap, C, ws, p, we[:, perm].contiguous().to(d), be.to(d), pos.to(d), g.to(d), b.to(d),
                                      wq[:, perm].contiguous().to(d)))
-    finally:
-        ops.tune("embed.lds", 6)
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert torch.equal(res[0][0], res[2][0]) and torch.equal(res[0][1], res[2][1])
     if dtype == torch.float16 and D == 192:
         # the ring depth of k_embed_qkv2 (round 5: 4 stages by default, counted vmcnt waits that leave the younger chunks' DMAs and the tile stores outstanding)
-        try:
-            ops.tune("embed.lds", 4)
+        with ops.tuning({"embed.lds": 4}):
             for ns in (2, 3, 5):
-                ops.tune("embed.stages", ns)
                 for hm in (0, D // 24):
-                    a_, b_ = ops.embed_qkv(fmap, C, ws, p, we[:, perm].contiguous().to(d), be.to(d), pos.to(d), g.to(d), b.to(d), wq[:, perm].contiguous().to(d),
-                                           head_major_heads=hm)
-                    ops.tune("embed.stages", 4)
-                    c_, d_ = ops.embed_qkv(fmap, C, ws, p, we[:, perm].contiguous().to(d), be.to(d), pos.to(d), g.to(d), b.to(d), wq[:, perm].contiguous().to(d),
-                                           head_major_heads=hm)
-                    ops.tune("embed.stages", ns)
+                    args = (fmap, C, ws, p, we[:, perm].contiguous().to(d), be.to(d), pos.to(d), g.to(d), b.to(d), wq[:, perm].contiguous().to(d))
+                    with ops.tuning({"embed.stages": ns}):
+                        a_, b_ = ops.embed_qkv(*args, head_major_heads=hm)
+                    with ops.tuning({"embed.stages": 4}):
+                        c_, d_ = ops.embed_qkv(*args, head_major_heads=hm)
                     assert torch.equal(a_, c_) and torch.equal(b_, d_), "embed.stages %d differs from 4" % ns
-        finally:
-            ops.tune("embed.stages", 4)
-            ops.tune("embed.lds", 6)
     x1, qkv = res[1]
     # head-major store (input layout of cfen_attention_head_major): the same values, laid out per (window, head)
     heads = D // 24
     nwin = B * (H // ws) * (W // ws)
     for lds in (0, 3, 4):
-        ops.tune("embed.lds", lds)
-        try:
+        with ops.tuning({"embed.lds": lds}):
             x1h, qkvh = ops.embed_qkv(fmap, C, ws, p, we[:, perm].contiguous().to(d), be.to(d), pos.to(d), g.to(d), b.to(d),
                                       wq[:, perm].contiguous().to(d), head_major_heads=heads)
-        finally:
-            ops.tune("embed.lds", 6)
         assert torch.equal(x1h, x1) and torch.equal(qkvh.view(-1), to_head_major(qkv, nwin, S, heads))
     tok = ops.patchify(fmap, C, ws, p)
     t64 = tok.double().cpu()
@@ -617,12 +593,9 @@ def test_conv_gather_with_and_without_lds_staged_weights_is_bitwise_equal(dtype)
     w1, b1 = rnd((24, 48, 1, 1), 7, dtype, 1 / math.sqrt(48)), rnd((24,), 8, torch.float32, 0.1)
     anw, anb = rnd((24,), 9, torch.float32, 0.2), rnd((24,), 10, torch.float32, 0.2)
     outs = {}
-    try:
-        for mode in (2, 1, 0):
-            ops.tune("conv.wlds", mode)
+    for mode in (2, 1, 0):
+        with ops.tuning({"conv.wlds": mode}):
             outs[mode] = (run_conv(dtype, x, w3, b3, 3, 2, 1, act=1), run_conv(dtype, a, w1, b1, 1, 1, 0, an=(anw, anb), act=1, res=res, x2=b2))
-    finally:
-        ops.tune("conv.wlds", 2)
     for mode in (1, 0):
         assert torch.equal(outs[mode][0], outs[2][0]) and torch.equal(outs[mode][1], outs[2][1]), mode
     close(outs[2][0], torch.relu(F.conv2d(x.double(), w3.double(), b3.double(), stride=2, padding=1)), tol(dtype, 6))
@@ -649,34 +622,30 @@ def test_multi_tile_workgroups_of_conv7_and_convT_cover_ragged_tile_counts():
     """k_conv7_tz walks `conv7.tpw` tiles per workgroup and the 128-byte k_convT_tile `convT.tpw` (weights loaded once per workgroup) when the
     launch has enough tiles; tile counts that do not divide (the last workgroup stops early) must give bitwise the one-tile-per-workgroup result"""
     dtype, d = torch.float16, dev()
-    try:
-        # conv7: 5 x (1040 / 16) x (576 / 64) = 2925 tiles (odd) -> up to 2 tiles per workgroup (2925 / 1024; the knob value 3 is clamped to 2)
-        x = rnd((5, 12, 1040, 576), 1, dtype)
-        w = rnd((3, 12, 7, 7), 2, dtype, 0.3 / math.sqrt(12 * 49))
-        s, t = packing.affine(rnd((3,), 3, torch.float32, 0.1), cout_pad=16)
-        xn, wz = ops.to_nhwc(x).to(d), packing.pack_conv7_toeplitz(w, dtype)[0].to(d)
-        outs = {}
-        for tpw in (1, 2, 3):
-            ops.tune("conv7.tpw", tpw)
+    # conv7: 5 x (1040 / 16) x (576 / 64) = 2925 tiles (odd) -> up to 2 tiles per workgroup (2925 / 1024; the knob value 3 is clamped to 2)
+    x = rnd((5, 12, 1040, 576), 1, dtype)
+    w = rnd((3, 12, 7, 7), 2, dtype, 0.3 / math.sqrt(12 * 49))
+    s, t = packing.affine(rnd((3,), 3, torch.float32, 0.1), cout_pad=16)
+    xn, wz = ops.to_nhwc(x).to(d), packing.pack_conv7_toeplitz(w, dtype)[0].to(d)
+    outs = {}
+    for tpw in (1, 2, 3):
+        with ops.tuning({"conv7.tpw": tpw}):
             outs[tpw] = ops.conv2d(xn, wz, s.to(d), t.to(d), 16, 3, k=7, stride=1, pad=3, reflect=True, act=2, nchw_f32=True, toeplitz=True).cpu()
-        assert torch.equal(outs[1], outs[2]) and torch.equal(outs[1], outs[3])
-        last = slice(4, 5)      # the image the ragged last workgroup writes: against torch (affine = scale 1, shift = bias)
-        want = torch.tanh(F.conv2d(F.pad(x[last].double(), (3, 3, 3, 3), mode="reflect"), w.double(), t[:3].double()))
-        close(outs[2][last], want, tol(dtype, 2))
-        # convT (48 -> 24 channels: the 128-byte variant): 3 x (1028 / 4) x (96 / 32) = 2313 tiles (odd) -> 2 tiles per workgroup
-        cin, cout = 48, 24
-        xt = rnd((3, cin, 1028, 96), 4, dtype)
-        wt = rnd((cin, cout, 4, 4), 5, dtype, 1 / math.sqrt(cin * 4))
-        st, tt = packing.affine(rnd((cout,), 6, torch.float32, 0.1), cout_pad=packing.round_up(cout, 16))
-        xtn, wr = ops.to_nhwc(xt).to(d), packing.pack_convT_weight_rows(wt, packing.cs_of(cin), dtype).to(d)
-        outs = {}
-        for tpw in (1, 2):
-            ops.tune("convT.tpw", tpw)
+    assert torch.equal(outs[1], outs[2]) and torch.equal(outs[1], outs[3])
+    last = slice(4, 5)      # the image the ragged last workgroup writes: against torch (affine = scale 1, shift = bias)
+    want = torch.tanh(F.conv2d(F.pad(x[last].double(), (3, 3, 3, 3), mode="reflect"), w.double(), t[:3].double()))
+    close(outs[2][last], want, tol(dtype, 2))
+    # convT (48 -> 24 channels: the 128-byte variant): 3 x (1028 / 4) x (96 / 32) = 2313 tiles (odd) -> 2 tiles per workgroup
+    cin, cout = 48, 24
+    xt = rnd((3, cin, 1028, 96), 4, dtype)
+    wt = rnd((cin, cout, 4, 4), 5, dtype, 1 / math.sqrt(cin * 4))
+    st, tt = packing.affine(rnd((cout,), 6, torch.float32, 0.1), cout_pad=packing.round_up(cout, 16))
+    xtn, wr = ops.to_nhwc(xt).to(d), packing.pack_convT_weight_rows(wt, packing.cs_of(cin), dtype).to(d)
+    outs = {}
+    for tpw in (1, 2):
+        with ops.tuning({"convT.tpw": tpw}):
             outs[tpw] = ops.conv2d(xtn, wr, st.to(d), tt.to(d), packing.cs_of(cin), cout, transpose=True, act=1, rows_layout=True).cpu()
-        assert torch.equal(outs[1], outs[2])
-    finally:
-        ops.tune("conv7.tpw", 4)
-        ops.tune("convT.tpw", 2)
+    assert torch.equal(outs[1], outs[2])
 
 
 @pytest.mark.parametrize("cin,cout,H,W", [(96, 48, 8, 32), (48, 24, 12, 64), (24, 12, 16, 96)])
@@ -819,16 +788,13 @@ def test_mlp_stream_block(D, H, M):
     if D == 192:
         # the workgroup shapes of the D = 192 variant (default 22: two 78 KB workgroups a CU on a three-slot ring, 256 registers; 24: four slots; 2 / 3 / 4 token
         # tiles a wave on the six-slot ring of one workgroup a CU) do the same arithmetic per token in the same order
-        try:
-            for tm in (24, 3, 4, 2):
-                ops.tune("mlp3.tm192", tm)
+        for tm in (24, 3, 4, 2):
+            with ops.tuning({"mlp3.tm192": tm}):
                 other = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H, ln=(g.to(d), b.to(d)), second=(sb, b1b.to(d), b2b.to(d)), proj=(att.to(d), sp))
                 if tm == 2:     # (the two-tile shape on 512 registers: hipcc contracts one epilogue product differently -- 1 fp16 ulp on a handful of elements)
                     assert float((got.float() - other.float()).abs().max()) <= 2e-3
                 else:
                     assert torch.equal(got, other), "mlp3.tm192 = %d differs from the default shape" % tm
-        finally:
-            ops.tune("mlp3.tm192", 22)
 
 
 def test_mlp_stream_fold_epilogue():
@@ -869,18 +835,15 @@ def test_mlp_stream_pair_kernel(H, M, fold):
                                                        + b1.double()) @ w2.double().t() + b2.double()
     full = ffn(ffn(x.double() + att.double() @ wp.double().t(), w1a, b1a, w2a, b2a, True), w1b, b1b, w2b, b2b, False)
     call = lambda **kw: ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H, ln=(g.to(d), b.to(d)), second=(sb, b1b.to(d), b2b.to(d)), proj=(att.to(d), sp), **kw)
-    try:
-        ops.tune("mlp3.pair", 1)
+    with ops.tuning({"mlp3.pair": 1}):
         got = call()
         close(got, full, tol(dtype, 12), "pair kernel")
         assert torch.equal(got, call())
         if fold:
             assert torch.equal(call(fold=(B, Hm, Wm, C, cs, ws, pp)), ops.unpatchify(got, B, Hm, Wm, C, cs, ws, pp))
-        ops.tune("mlp3.pair", 0)
+    with ops.tuning({"mlp3.pair": 0}):
         single = call()
-        assert float((got.float() - single.float()).abs().max()) <= 2 ** -7 * max(1.0, float(single.float().abs().max()) / 4)
-    finally:
-        ops.tune("mlp3.pair", 1)
+    assert float((got.float() - single.float()).abs().max()) <= 2 ** -7 * max(1.0, float(single.float().abs().max()) / 4)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -912,13 +875,10 @@ def test_lvit_window_block_against_oracle_and_unfused_chain(B, H, W):
     got = ops.from_nhwc(ops.lvit_window(fmap, 24, 32, 2, pk, g.name, g.hidden), 24)
     close(got, want, tol(dt, 12), "fused window block vs fp64")
     # the three workgroup shapes (16 waves x 1 token tile: the default; 8 x 2; 4 x 4 on 512 registers) do the same arithmetic per token
-    try:
-        for shape in (0, 1, 12, 15, 4, 6):       # 12: the refill right behind the barrier; 15: double MLP chunks over the dead K / V tiles (round 6)          # 6: the embedding / K, V matrices in 64-row chunks (5 front chunks instead of 9)          # 4: the attention loops' K / V fragment reads issued by hand ahead of the MFMAs (round 5): same arithmetic, same order
-            ops.tune("lvit.shape", shape)
+    for shape in (0, 1, 12, 15, 4, 6):       # 12: the refill right behind the barrier; 15: double MLP chunks over the dead K / V tiles (round 6)          # 6: the embedding / K, V matrices in 64-row chunks (5 front chunks instead of 9)          # 4: the attention loops' K / V fragment reads issued by hand ahead of the MFMAs (round 5): same arithmetic, same order
+        with ops.tuning({"lvit.shape": shape}):
             other = ops.from_nhwc(ops.lvit_window(fmap, 24, 32, 2, pk, g.name, g.hidden), 24)
             assert torch.equal(other, got), "lvit.shape %d differs from the default shape" % shape
-    finally:
-        ops.tune("lvit.shape", 2)
     # the unfused chain (embed_qkv -> attention -> mlp with projection prologue + fold)
     n = g.name
     x1, qkv = ops.embed_qkv(fmap, 24, 32, 2, pk[n + ".embed.wk"], pk[n + ".embed.b"], pk[n + ".pos"], pk[n + ".ln1.g"], pk[n + ".ln1.b"],

@@ -32,12 +32,11 @@ for name, M, N, K in shapes:
     r = None; out = torch.empty(M, N, device=d).half()
     res = []
     for v in VARIANTS:
-        ops.tune("gemm.kernel", v)
-        try:
-            res.append(timeit(lambda: ops.gemm_nt(x, w, bias=b, residual=r, out=out)))
-        except Exception:
-            res.append(float("inf"))
-    ops.tune("gemm.kernel", -1)
+        with ops.tuning({"gemm.kernel": v}):
+            try:
+                res.append(timeit(lambda: ops.gemm_nt(x, w, bias=b, residual=r, out=out)))
+            except Exception:
+                res.append(float("inf"))
     auto = timeit(lambda: ops.gemm_nt(x, w, bias=b, residual=r, out=out))
     fl = 2.0 * M * N * K
     print("%-16s %7d %6d %6d | " % (name, M, N, K) + " ".join("%9.1f" % r for r in res) + " | %s %.0f TF (auto %.1f us)" % (NAMES[res.index(min(res))], fl / min(res) / 1e6, auto))

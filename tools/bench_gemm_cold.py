@@ -26,8 +26,8 @@ junk = torch.empty(256 * 1024 * 1024, dtype=torch.uint8, device=d)
 for name, M, N, K in SHAPES:
     x = torch.randn(M, K, device=d).half(); w = (torch.randn(N, K, device=d) * 0.05).half(); out = torch.empty(M, N, device=d).half()
     for v in VARIANTS:
-        ops.tune("gemm.kernel", v)
-        for _ in range(REPS):
-            junk.fill_(1)
-            ops.gemm_nt(x, w, out=out)
+        with ops.tuning({"gemm.kernel": v}):
+            for _ in range(REPS):
+                junk.fill_(1)
+                ops.gemm_nt(x, w, out=out)
     torch.cuda.synchronize()

@@ -33,19 +33,18 @@ for D, M, variants in ((96, 131072, (3, 10, 20, 30, 40)), (96, 3 * 131072, (3, 1
     run = lambda: ops.mlp_block(x, *ws[:4], ln=(lg, lb), second=tuple(ws[4:]), proj=(att, wp))
     ref, times = None, {v: [] for v in variants}
     for v in variants:
-        ops.tune("mlp.small_tiles", v)
-        y = run()
-        torch.cuda.synchronize()
+        with ops.tuning({"mlp.small_tiles": v}):
+            y = run()
+            torch.cuda.synchronize()
         if ref is None:
             ref = y.float()
         else:
             print("   D=%d M=%d variant %d vs variant %d: max-abs %.3e" % (D, M, v, variants[0], float((y.float() - ref).abs().max())))
     for rnd in range(7):
         for v in variants:
-            ops.tune("mlp.small_tiles", v)
-            times[v].append(timed(run))
+            with ops.tuning({"mlp.small_tiles": v}):
+                times[v].append(timed(run))
     fl = (8.0 * H + 2.0 * D) * M * D
     for v in variants:
         t = sorted(times[v])
         print("D=%d M=%d variant %2d: median %.1f us (min %.1f)  %.0f TF/s" % (D, M, v, t[len(t) // 2], t[0], fl / t[len(t) // 2] / 1e6))
-ops.tune("mlp.small_tiles", 10)

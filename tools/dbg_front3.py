@@ -40,19 +40,18 @@ def main():
         se, sq = packing.pack_stream_rows(we[:, kd].contiguous()), packing.pack_stream_rows(wq[:, kd].contiguous())
         call = lambda: ops.embed_qkv(fmap, C, ws, p, se, be, pos, g, b, sq, head_major_heads=16, stream_weights=True)
         fl = 8.0 * M * D * D
-        ops.tune("front3.debug", 0)
-        med, best = timeit(call)
+        with ops.tuning({"front3.debug": 0}):
+            med, best = timeit(call)
         print("M=%d (%d workgroups): shipped %.1f us median / %.1f best = %.0f TF" % (M, M // 128, med, best, fl / med / 1e6), flush=True)
         for v, nm in ((1, "no refills"), (8, "no qkv stores"), (24, "no stores at all")):
-            ops.tune("front3.debug", v)
-            med, best = timeit(call)
+            with ops.tuning({"front3.debug": v}):
+                med, best = timeit(call)
             print("  debug=%-3d %-20s %.1f us median / %.1f best" % (v, nm, med, best), flush=True)
         for v in (64, 64 + 1, 64 + 8, 64 + 24):
             sys.stderr.write("==== M=%d stamped, debug=%d\n" % (M, v)); sys.stderr.flush()
-            ops.tune("front3.debug", v)
-            for _ in range(2):
-                flush.fill_(1); call(); torch.cuda.synchronize()
-        ops.tune("front3.debug", 0)
+            with ops.tuning({"front3.debug": v}):
+                for _ in range(2):
+                    flush.fill_(1); call(); torch.cuda.synchronize()
 
 
 if __name__ == "__main__":

@@ -31,9 +31,8 @@ def timed(f, n=9):
 for B in (8, 24):
     x = (torch.rand(B, 256, 256, 24, generator=torch.Generator().manual_seed(1)) * 2 - 1).half().to(d)
     for shape in (0, 1):
-        ops.tune("lvit.shape", shape)
-        full = timed(lambda: ops.lvit_window(x, 24, 32, 2, pk, n, 384))
-        one = timed(lambda: ops.lvit_window(x, 24, 32, 2, small, n, 32))
+        with ops.tuning({"lvit.shape": shape}):
+            full = timed(lambda: ops.lvit_window(x, 24, 32, 2, pk, n, 384))
+            one = timed(lambda: ops.lvit_window(x, 24, 32, 2, small, n, 32))
         print("B=%d shape %d: hidden 384 %.1f us, hidden 32 %.1f us -> 22 more MLP chunks cost %.1f us (%.2f us per chunk and round of workgroups)"
               % (B, shape, full, one, full - one, (full - one) / 22 / (B * 64 / 256)), flush=True)
-ops.tune("lvit.shape", 0)

@@ -33,14 +33,11 @@ shapes = [int(v) for v in sys.argv[1:]] or [2]
 for B in (8, 24):
     x = (torch.rand(B, 256, 256, 24, generator=torch.Generator().manual_seed(1)) * 2 - 1).half().to(d)
     for shape in shapes:
-        ops.tune("lvit.shape", shape)
-        ops.tune("lvit.debug", 0)
         call = lambda: ops.lvit_window(x, 24, 32, 2, pk, g.name, 384)
-        call(); torch.cuda.synchronize()
-        print("B=%d (%d windows) lvit.shape %d: %.1f us" % (B, B * 64, shape, timed(call)), flush=True)
-        sys.stderr.write("==== B=%d lvit.shape %d\n" % (B, shape)); sys.stderr.flush()
-        ops.tune("lvit.debug", 64)
-        for _ in range(2):
-            flush.zero_(); call(); torch.cuda.synchronize()
-        ops.tune("lvit.debug", 0)
-ops.tune("lvit.shape", 2)
+        with ops.tuning({"lvit.shape": shape, "lvit.debug": 0}):
+            call(); torch.cuda.synchronize()
+            print("B=%d (%d windows) lvit.shape %d: %.1f us" % (B, B * 64, shape, timed(call)), flush=True)
+            sys.stderr.write("==== B=%d lvit.shape %d\n" % (B, shape)); sys.stderr.flush()
+            with ops.tuning({"lvit.debug": 64}):
+                for _ in range(2):
+                    flush.zero_(); call(); torch.cuda.synchronize()

@@ -22,7 +22,6 @@ for M in (128, 8192, 24576, 32768):
     sa, sp = packing.pack_stream_pair(w1[:, kd], w2[:, kh]), packing.pack_stream_sq(wp)
     res = []
     for dbg in (0, 1, 2):
-        ops.tune("mlp3.debug", dbg)
-        res.append(round(timeit(lambda: ops.mlp_stream_block(x, sa, b1, b2, H, ln=(g, b), second=(sa, b1, b2), proj=(att, sp))), 1))
-    ops.tune("mlp3.debug", 0)
+        with ops.tuning({"mlp3.debug": dbg}):
+            res.append(round(timeit(lambda: ops.mlp_stream_block(x, sa, b1, b2, H, ln=(g, b), second=(sa, b1, b2), proj=(att, sp))), 1))
     print("M=%d: full %.1f us, no DMA refill %.1f us, no MFMA %.1f us" % (M, *res), flush=True)

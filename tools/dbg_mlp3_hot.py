@@ -23,9 +23,8 @@ for H in (256, 768, 1536):
     sa = packing.pack_stream_pair(w1[:, kd], w2[:, kh])
     res = []
     for dbg in (0, 2):
-        ops.tune("mlp3.debug", dbg)
-        for cold in (False, True):
-            res.append(round(timeit(lambda: ops.mlp_stream_block(x, sa, b1, b2, H, second=(sa, b1, b2)), cold=cold), 1))
-    ops.tune("mlp3.debug", 0)
+        with ops.tuning({"mlp3.debug": dbg}):
+            for cold in (False, True):
+                res.append(round(timeit(lambda: ops.mlp_stream_block(x, sa, b1, b2, H, second=(sa, b1, b2)), cold=cold), 1))
     nph = 4 * H // 32
     print("H=%d M=%d (%d phases): full hot %.1f cold %.1f | no-MFMA hot %.1f cold %.1f us  -> per phase %.2f / %.2f us" % (H, M, nph, *res, res[2] / nph, res[3] / nph), flush=True)

@@ -27,31 +27,30 @@ for M in (1000, 2048, 24576):
     kd, kh = packing.kperm32(D).to(d), packing.kperm32(H).to(d)
     sa, sb, sp = packing.pack_stream_pair(w1a[:, kd], w2a[:, kh]), packing.pack_stream_pair(w1b[:, kd], w2b[:, kh]), packing.pack_stream_sq(wp)
     call = lambda: ops.mlp_stream_block(x, sa, b1a, b2a, H, ln=(g, b), second=(sb, b1b, b2b), proj=(att, sp))
-    ops.tune("mlp3.pair", 0)
-    ref = call().float()
+    with ops.tuning({"mlp3.pair": 0}):
+        ref = call().float()
+        t0 = timeit(call)
     # fp64 reference
     X = x.double() + att.double() @ wp.double().t()
     mu = X.mean(1, keepdim=True); var = ((X - mu) ** 2).mean(1, keepdim=True)
     Ln = (X - mu) / torch.sqrt(var + 1e-5) * g.double() + b.double()
     Y1 = X + torch.relu(Ln.half().double() @ w1a.double().t() + b1a.double()).half().double() @ w2a.double().t() + b2a.double()
     Y2 = Y1 + torch.relu(Y1.half().double() @ w1b.double().t() + b1b.double()).half().double() @ w2b.double().t() + b2b.double()
-    t0 = timeit(call)
-    ops.tune("mlp3.pair", 1)
-    out = call().float()
-    torch.cuda.synchronize()
-    again = call().float()
-    t1 = timeit(call)
-    print("   warm caches (no 256 MiB fill between launches): pair %.1f us" % timeit(call, cold=False), flush=True)
-    for v in VARIANTS:
-        ops.tune("mlp3.pair", v)
-        o2 = call().float()
+    with ops.tuning({"mlp3.pair": 1}):
+        out = call().float()
         torch.cuda.synchronize()
-        o3 = call().float()
-        print("   variant %d: %.1f us (max |. - pair| %.3e, vs fp64 %.3e, deterministic %s)" % (v, timeit(call), float((o2 - out).abs().max()), float((o2.double() - Y2).abs().max()), bool(torch.equal(o2, o3))), flush=True)
+        again = call().float()
+        t1 = timeit(call)
+        print("   warm caches (no 256 MiB fill between launches): pair %.1f us" % timeit(call, cold=False), flush=True)
+    for v in VARIANTS:
+        with ops.tuning({"mlp3.pair": v}):
+            o2 = call().float()
+            torch.cuda.synchronize()
+            o3 = call().float()
+            print("   variant %d: %.1f us (max |. - pair| %.3e, vs fp64 %.3e, deterministic %s)" % (v, timeit(call), float((o2 - out).abs().max()), float((o2.double() - Y2).abs().max()), bool(torch.equal(o2, o3))), flush=True)
     sys.stderr.write("==== M=%d\n" % M); sys.stderr.flush()
-    ops.tune("mlp3.pair", STAMPED)
-    for _ in range(2):
-        flush.fill_(1); call(); torch.cuda.synchronize()
-    ops.tune("mlp3.pair", 0)
+    with ops.tuning({"mlp3.pair": STAMPED}):
+        for _ in range(2):
+            flush.fill_(1); call(); torch.cuda.synchronize()
     e_ref = float((ref.double() - Y2).abs().max()); e_pair = float((out.double() - Y2).abs().max())
     print("M=%d: shipped %.1f us, pair %.1f us; max|pair - shipped| %.3e; vs fp64: shipped %.3e pair %.3e; pair deterministic %s" % (M, t0, t1, float((out - ref).abs().max()), e_ref, e_pair, bool(torch.equal(out, again))), flush=True)

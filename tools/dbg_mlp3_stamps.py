@@ -45,33 +45,32 @@ def main():
         sa, sb, sp = packing.pack_stream_pair(w1a[:, kd], w2a[:, kh]), packing.pack_stream_pair(w1b[:, kd], w2b[:, kh]), packing.pack_stream_sq(wp)
         fl = (8.0 * D * H + 2.0 * D * D) * M
         call = lambda: ops.mlp_stream_block(x, sa, b1, b2, H, ln=(g, b), second=(sb, b1, b2), proj=(att, sp))
-        ops.tune("mlp3.debug", 0)
-        ref = call().clone()
-        med, best = timeit(call)
+        with ops.tuning({"mlp3.debug": 0}):
+            ref = call().clone()
+            med, best = timeit(call)
         print("M=%d (%d workgroups): shipped %.1f us median / %.1f best = %.0f TF" % (M, M // 128, med, best, fl / med / 1e6), flush=True)
         for v in want:
-            try:
-                ops.tune("mlp3.debug", v)
-                out = call()
-            except Exception as ex:  # a variant this build does not carry
-                print("  debug=%d: %s" % (v, ex))
-                continue
-            same = bool(torch.equal(out, ref))
-            med, best = timeit(call)
+            with ops.tuning({"mlp3.debug": v}):
+                try:
+                    out = call()
+                except Exception as ex:  # a variant this build does not carry
+                    print("  debug=%d: %s" % (v, ex))
+                    continue
+                same = bool(torch.equal(out, ref))
+                med, best = timeit(call)
             print("  debug=%-3d %-40s %.1f us median / %.1f best = %.0f TF   bitwise equal to shipped: %s" % (v, NAMES.get(v, "?"), med, best, fl / med / 1e6, same), flush=True)
         if M in (2048, 24576):
             for v, nm in STAMPED.items():
                 sys.stderr.write("==== M=%d stamped build %d (%s)\n" % (M, v, nm))
                 sys.stderr.flush()
                 try:
-                    ops.tune("mlp3.debug", v)
-                    for _ in range(3):
-                        flush.fill_(1)
-                        call()
-                        torch.cuda.synchronize()
+                    with ops.tuning({"mlp3.debug": v}):
+                        for _ in range(3):
+                            flush.fill_(1)
+                            call()
+                            torch.cuda.synchronize()
                 except Exception as ex:
                     sys.stderr.write("  %s\n" % ex)
-        ops.tune("mlp3.debug", 0)
 
 
 if __name__ == "__main__":

@@ -20,10 +20,10 @@ ffn = lambda v, w1, b1, w2, b2, ln: v + torch.relu((cfen_oracle.layer_norm(v, g.
 full = ffn(ffn(xd + att.double() @ wp.double().t(), w1a, b1a, w2a, b2a, True), w1b, b1b, w2b, b2b, False)
 res = {}
 for tm in (22, 24, 2, 3, 4):
-    ops.tune("mlp3.tm192", tm)
-    res[tm] = {}
-    res[tm]["full"] = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H, ln=(g.to(d), b.to(d)), second=(sb, b1b.to(d), b2b.to(d)), proj=(att.to(d), sp)).float().cpu()
-    res[tm]["noln"] = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H).float().cpu()
-    res[tm]["ln"] = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H, ln=(g.to(d), b.to(d))).float().cpu()
+    with ops.tuning({"mlp3.tm192": tm}):
+        res[tm] = {}
+        res[tm]["full"] = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H, ln=(g.to(d), b.to(d)), second=(sb, b1b.to(d), b2b.to(d)), proj=(att.to(d), sp)).float().cpu()
+        res[tm]["noln"] = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H).float().cpu()
+        res[tm]["ln"] = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H, ln=(g.to(d), b.to(d))).float().cpu()
 for tm in res:
     print(tm, "vs fp64 %.3e" % float((res[tm]["full"].double() - full).abs().max()), {k: "%.3e (%d elems)" % (float((res[tm][k] - res[22][k]).abs().max()), int((res[tm][k] != res[22][k]).sum())) for k in res[tm]})

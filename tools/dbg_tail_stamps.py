@@ -15,7 +15,6 @@ ops.tune("tail.segments", int(sys.argv[1]) if len(sys.argv) > 1 else 4)
 for _ in range(2): net(x)
 torch.cuda.synchronize()
 sys.stderr.write("==== stamped forward\n")
-ops.tune("tail.debug", 64)
-net(x)
-torch.cuda.synchronize()
-ops.tune("tail.debug", 0)
+with ops.tuning({"tail.debug": 64}):
+    net(x)
+    torch.cuda.synchronize()
