@@ -289,6 +289,13 @@ int cfen_image_metrics(int u8, const void* a, const void* b, int B, int C, int H
                        void* stream) {
   return cfen_image_metrics_impl(u8, a, b, B, C, H, W, lo, hi, scratch, out, (hipStream_t)stream);
 }
+size_t cfen_png_workspace_bytes(int B, int H, int W, size_t* strip_bytes, size_t* out_stride) {
+  return cfen_png_workspace_bytes_impl(B, H, W, strip_bytes, out_stride);
+}
+int cfen_png_deflate(const unsigned char* images, int B, int H, int W, const void* tables, int n_tables, void* workspace, unsigned char* out,
+                     int* out_lengths, void* stream) {
+  return cfen_png_deflate_impl(images, B, H, W, tables, n_tables, workspace, out, out_lengths, (hipStream_t)stream);
+}
 int cfen_tile_gather(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, void* stream) {
   return cfen_tile_gather_impl(u8, src, dst, H, W, T, ny, nx, t0, B, (hipStream_t)stream);
 }

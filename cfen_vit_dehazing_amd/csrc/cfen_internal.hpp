@@ -73,6 +73,9 @@ int cfen_tensor2im_u8_impl(const float* in, unsigned char* out, int C, int H, in
 size_t cfen_image_metrics_bytes_impl(int B, int C, int H, int W);
 int cfen_image_metrics_impl(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
                             hipStream_t s);
+size_t cfen_png_workspace_bytes_impl(int B, int H, int W, size_t* strip_bytes, size_t* out_stride);
+int cfen_png_deflate_impl(const unsigned char* images, int B, int H, int W, const void* tables, int n_tables, void* workspace, unsigned char* out,
+                          int* out_lengths, hipStream_t s);
 int cfen_tile_gather_impl(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, hipStream_t s);
 int cfen_tile_blend_impl(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs,
                          void* xd, hipStream_t s);

@@ -445,6 +445,33 @@ def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     return out[:, 0], out[:, 1]      # (scratch goes back to torch's allocator on the stream it was used on)
 
 
+def png_deflate(images, out=None, out_lengths=None):
+    """cfen_png_deflate: contiguous (B,H,W,3) uint8 CUDA images -> (slab, lengths): slab (B, out_stride) uint8 holds image b's finished zlib
+    stream (the IDAT payload of an 8-bit RGB PNG, png.assemble adds the container) in slab[b, :lengths[b]]; lengths (B,) int32.  The candidate
+    Huffman tables (png.py) are uploaded once per device.  CfenError for an image wider than the encoder's strip (png.geometry)."""
+    from . import png
+    _cuda(images, out, out_lengths)
+    if images.dim() != 4 or images.shape[3] != 3 or images.dtype != torch.uint8 or not images.is_contiguous():
+        raise ValueError("png_deflate needs a contiguous (B,H,W,3) uint8 tensor, got %s %s" % (tuple(images.shape), images.dtype))
+    B, H, W, _ = images.shape
+    lib = _lib.load()
+    strip, stride = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    nbytes = lib.cfen_png_workspace_bytes(B, H, W, ctypes.byref(strip), ctypes.byref(stride))
+    tables = png.device_tables(images.device)
+    workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=images.device)
+    if out is None:
+        out = torch.empty(B, max(stride.value, 16), dtype=torch.uint8, device=images.device)
+    elif nbytes and (tuple(out.shape) != (B, stride.value) or out.dtype != torch.uint8 or not out.is_contiguous()):
+        raise ValueError("png_deflate: out must be a contiguous (%d, %d) uint8 CUDA tensor" % (B, stride.value))
+    if out_lengths is None:
+        out_lengths = torch.empty(B, dtype=torch.int32, device=images.device)
+    elif tuple(out_lengths.shape) != (B,) or out_lengths.dtype != torch.int32 or not out_lengths.is_contiguous():
+        raise ValueError("png_deflate: out_lengths must be a contiguous (%d,) int32 CUDA tensor" % B)
+    check(lib.cfen_png_deflate(ptr(images), B, H, W, ptr(tables), tables.shape[0], ptr(workspace), ptr(out), ptr(out_lengths), current_stream()),
+          "png_deflate")
+    return out, out_lengths      # (workspace goes back to torch's allocator on the stream it was used on)
+
+
 def u8hwc_to_nhwc(img, cs, dtype):
     """(B,H,W,3) uint8 CUDA tensor -> normalised NHWC [B,H,W,cs] of `dtype` (ToTensor + Normalize(0.5, 0.5) + layout)"""
     _cuda(img)

@@ -76,6 +76,10 @@ class BaseOptions():
         p.add_argument('--writer_procs', type=int, default=0,
                        help='(extension) PNG encoder PROCESSES of the pipelined driver instead of --writers threads (0 = threads): forked right after option parsing, images '
                             'handed over through shared memory; encode scales with the host cores (threads contend for the GIL around the compressor)')
+        p.add_argument('--gpu_png', action='store_true',
+                       help='(extension) encode the result PNGs on the device (cfen_vit_dehazing_amd/png.py: per-strip filtering and Huffman coding, no LZ77): '
+                            'the same pixels in larger files that are not byte-identical to PIL\'s; the host only adds the container and its CRC. Not with '
+                            '--writer_procs or --png_compress_level')
         p.add_argument('--u8_input', action='store_true',
                        help='(extension) the dataset hands over uint8 HWC images and ToTensor + Normalize(0.5, 0.5) run on the device '
                             'inside the generator launch plan (12x fewer bytes over PCIe); results are identical')
@@ -140,6 +144,8 @@ class BaseOptions():
                                  'cover the dataset in order')
         if not -1 <= opt.png_compress_level <= 9:
             raise ValueError('--png_compress_level must be -1 (PIL default) or 0..9')
+        from .. import png as _png
+        _png.check_options(opt)
         from ..util import util as _util
         _util.PNG_COMPRESS_LEVEL = None if opt.png_compress_level < 0 else opt.png_compress_level      # set before any writer process is forked
         if opt.in_flight > 1:
@@ -152,6 +158,8 @@ class BaseOptions():
         args = vars(opt)
         if not getattr(opt, 'eval', False):
             args = {k: v for k, v in args.items() if k not in ('eval', 'gt_dir')}      # a run without --eval prints and records what it always did
+        if not getattr(opt, 'gpu_png', False):
+            args = {k: v for k, v in args.items() if k != 'gpu_png'}                   # ... and so does one without --gpu_png
         if opt.dist_rank == 0:
             print('------------ Options -------------')
             for k, v in sorted(args.items()):

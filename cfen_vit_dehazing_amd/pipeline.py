@@ -42,6 +42,16 @@ def _save_png(arr, path):
 _WRITERS = None
 
 
+def _write_file(data, path):
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def _write_png_stream(stream, H, W, path):
+    from . import png
+    png.write_stream(stream, H, W, path)
+
+
 def _save_png_from_ring(off, shape, path, token):
     arr = np.frombuffer(_WRITERS["ring"], dtype=np.uint8, count=int(np.prod(shape)), offset=off).reshape(shape)
     util.save_image(arr, path)
@@ -131,6 +141,9 @@ class PipelinedRunner:
             self.ring_pinned = int(rc) == 0 and self.ring_t[:nbytes].is_pinned()
             self.stats_ring = {"batch_slots": p["bslots"], "registered_as_pinned": bool(self.ring_pinned)}
         self.labels = ['fake_A'] if opt.out_all else list(model.visual_names)
+        # --gpu_png: the slot's stream encodes behind the replay (png.py, csrc/k_png.hip); the copy back is the fixed-stride slab of zlib streams and their
+        # lengths instead of raw pixels, and a writer thread only adds the container (one CRC-32) and writes
+        self.gpu_png = bool(getattr(opt, 'gpu_png', False))
         self.stats = {"batches": 0, "images": 0, "graph_batches": 0, "sequential_batches": 0}
         # several forwards in flight want ONE serial chain of launches per forward (what bench.py replays): 2.26 against 2.38 ms per step with
         # three in flight, because a fork / join inside each of several concurrent graphs crosses hardware queues (DESIGN: launch plan)
@@ -159,7 +172,17 @@ class PipelinedRunner:
         self.net.replica = 0
         B = batch.shape[0]
         n = self.net.cfg.image_size
-        b.host = {lab: torch.empty(B, n, n, 3, dtype=torch.uint8).pin_memory() for lab in self.labels}
+        if self.gpu_png:
+            from . import png
+            stride = png.geometry(n, n)[4]
+            b.png_dev = {lab: (torch.empty(B, stride, dtype=torch.uint8, device=self.dev), torch.empty(B, dtype=torch.int32, device=self.dev)) for lab in self.labels}
+            b.png_host = {lab: (torch.empty(B, stride, dtype=torch.uint8).pin_memory(), torch.empty(B, dtype=torch.int32).pin_memory()) for lab in self.labels}
+            with torch.cuda.stream(s.stream):                  # the encoder's workspace comes from the caching allocator: fill this stream's pool now
+                ops.png_deflate(torch.zeros(B, n, n, 3, dtype=torch.uint8, device=self.dev), *b.png_dev[self.labels[0]])
+            s.stream.synchronize()
+            b.host = {}
+        else:
+            b.host = {lab: torch.empty(B, n, n, 3, dtype=torch.uint8).pin_memory() for lab in self.labels}
         if s.event is None:
             s.event = torch.cuda.Event()
         s.by_shape[(tuple(batch.shape), batch.dtype)] = b
@@ -216,6 +239,21 @@ class PipelinedRunner:
             s.bslot = None
             if self.proc_errors:
                 raise self.proc_errors[0]
+            return
+        if self.gpu_png:
+            n = self.net.cfg.image_size
+            for i, path in enumerate(s.paths):
+                name = os.path.splitext(ntpath.basename(path))[0]
+                for lab in self.labels:
+                    slab, lengths = s.cur.png_host[lab]
+                    stream = slab[i, :int(lengths[i])].numpy().tobytes()       # the used part only: the pinned slab is reused as soon as this returns
+                    self.pending.append(self.pool.submit(_write_png_stream, stream, n, n, os.path.join(self.image_dir, '%s_%s.png' % (name, lab))))
+            bound = 8 * self.K * max(1, len(s.paths)) * len(self.labels)
+            s.paths = None
+            while self.pending and self.pending[0].done():
+                self.pending.pop(0).result()
+            if len(self.pending) > bound:
+                self._reap(keep=bound // 2)
             return
         own = {lab: np.array(s.cur.host[lab].numpy()) for lab in self.labels}      # one copy per visual: the pinned buffers are reused as soon as this returns
         for i, path in enumerate(s.paths):
@@ -298,6 +336,14 @@ class PipelinedRunner:
         t3 = time.perf_counter()
         visuals = self.model.get_current_visuals()
         paths = self.model.get_image_paths()
+        if self.gpu_png:
+            from . import png
+            for lab in self.labels:
+                u8 = png.visual_u8(visuals[lab])
+                for i, data in enumerate(png.encode(u8)):
+                    name = os.path.splitext(ntpath.basename(paths[i]))[0]
+                    self.pending.append(self.pool.submit(_write_file, data, os.path.join(self.image_dir, '%s_%s.png' % (name, lab))))
+            paths = []
         for i, path in enumerate(paths):
             name = os.path.splitext(ntpath.basename(path))[0]
             for lab in self.labels:
@@ -355,7 +401,13 @@ class PipelinedRunner:
                         s.bslot = self.bfree.get()              # blocks while the writers hold every batch slot: the backlog is the ring
                         host = self._host_views(s.bslot, B)
                     for lab in self.labels:
-                        host[lab].copy_(self._visual_u8(s, lab, B), non_blocking=True)
+                        if self.gpu_png:
+                            (dslab, dlen), (hslab, hlen) = b.png_dev[lab], b.png_host[lab]
+                            ops.png_deflate(self._visual_u8(s, lab, B), out=dslab, out_lengths=dlen)
+                            hslab.copy_(dslab, non_blocking=True)
+                            hlen.copy_(dlen, non_blocking=True)
+                        else:
+                            host[lab].copy_(self._visual_u8(s, lab, B), non_blocking=True)
                     s.event.record(s.stream)
                 s.paths = paths
                 self.model.note_unchecked(paths)

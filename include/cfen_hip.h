@@ -306,6 +306,29 @@ size_t cfen_image_metrics_bytes(int B, int C, int H, int W);
 int cfen_image_metrics(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
                        void* stream);
 
+/* PNG encoding of uint8 images on the device (csrc/k_png.hip; png.py, test.py --gpu_png): per image one finished zlib stream, the payload of the
+ * single IDAT chunk of an 8-bit RGB, non-interlaced PNG.  The caller adds signature, IHDR, the IDAT framing with its CRC-32, and IEND.
+ *   stream : 78 01 | per strip: one non-final deflate block, then an empty non-final stored block (000, pad to a byte, 00 00 FF FF) |
+ *            01 00 00 FF FF | Adler-32 of the filtered scanlines, big-endian.
+ *   strips : R = max(1, 32768 / (3 W + 1)) rows, the last may be shorter; a scanline longer than 32768 bytes is refused (CFEN_ERR_ARG): encode that
+ *            image on the host.
+ *   filter : per row the type among None, Sub, Up, Average, Paeth with the smallest sum of |signed residual| (v < 128 ? v : 256 - v), ties to the
+ *            lowest type; the row above row 0 is zeros.
+ *   block  : literals only.  The first cheapest of the n_tables candidate codes as a dynamic-Huffman block (cost = header bits + histogram . lengths,
+ *            the end-of-block symbol counted once), used only if strictly below a stored block's 8 n + 40 bits, n the strip's filtered bytes.
+ * images: (B,H,W,3) uint8, contiguous.  tables: n_tables (1 .. 16) x 384 uint32 words on the device, per table
+ *   word 0        bits of the block header (BFINAL 0, BTYPE 2, HLIT 257, HDIST 1 with that code's length 0, the code-length code, the lengths),
+ *   words 1..63   those bits, packed from the least significant bit of word 1 on,
+ *   words 64..320 symbol 0..255 and end-of-block: (length << 16) | code, the code bit-reversed for LSB-first packing; every length 1 .. 15 and the
+ *                 code complete (png.py makes them); words 321..383 zero.
+ * workspace: cfen_png_workspace_bytes(B, H, W, &strip_bytes, &out_stride) bytes, contents irrelevant before and after: a 16-byte record and a slot of
+ *   strip_bytes (n + 16 rounded up to 16, the stored worst case) per strip.  0 for dimensions the call refuses.
+ * out: B x out_stride bytes, the stream of image b from out + b * out_stride; out_lengths[b]: its length in bytes.  images, workspace and out
+ * 16-byte aligned.  No atomics on global memory, integer arithmetic: the same image gives the same bytes on every call, stream and batch size.   */
+size_t cfen_png_workspace_bytes(int B, int H, int W, size_t* strip_bytes, size_t* out_stride);
+int cfen_png_deflate(const unsigned char* images, int B, int H, int W, const void* tables, int n_tables, void* workspace, unsigned char* out,
+                     int* out_lengths, void* stream);
+
 /* Conv2d / ConvTranspose2d(4,2,1) as implicit GEMM with fused affine + activation + residuals.
  * kind 0: Conv2d(k, stride, pad) over nsrc (1..3) channel-concatenated inputs (src0 | src1 | src2, the concat is never
  * materialised: v3:488 torch.cat((local, global), 1); crs_gd4:854 cat of three); kind 1: ConvTranspose2d k4 s2 p1.

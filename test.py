@@ -24,6 +24,15 @@ from cfen_vit_dehazing_amd.options.test_options import TestOptions
 from cfen_vit_dehazing_amd.util import html
 from cfen_vit_dehazing_amd.util.visualizer import save_images
 
+def _save(opt, image_dir, visuals, paths):
+    if getattr(opt, 'gpu_png', False):
+        # --gpu_png: the device encodes (cfen_vit_dehazing_amd/png.py), the host adds the container; same pixels, other bytes
+        from cfen_vit_dehazing_amd import png
+        png.save_images(image_dir, visuals, paths)
+    else:
+        save_images(image_dir, visuals, paths, aspect_ratio=opt.aspect_ratio, width=opt.display_winsize)
+
+
 def _rerun_in_fp32(opt, model, image_dir, paths):
     """images whose files came from fp16 forwards later found unsafe (--precision half, a periodic check failed): the model has switched to fp32, run them again"""
     import torch.utils.data
@@ -38,7 +47,7 @@ def _rerun_in_fp32(opt, model, image_dir, paths):
         if opt.out_all:
             for item in [k for k in visuals if 'fake_A' not in k]:
                 del visuals[item]
-        save_images(image_dir, visuals, model.get_image_paths(), aspect_ratio=opt.aspect_ratio, width=opt.display_winsize)
+        _save(opt, image_dir, visuals, model.get_image_paths())
 
 
 if __name__ == '__main__':
@@ -117,7 +126,7 @@ if __name__ == '__main__':
             img_path = model.get_image_paths()
             if i % 5 == 0:
                 logging.info('processing (%04d)-th image...' % (i * opt.batchSize))
-            save_images(webpage.get_image_dir(), visuals, img_path, aspect_ratio=opt.aspect_ratio, width=opt.display_winsize)
+            _save(opt, webpage.get_image_dir(), visuals, img_path)
         t_loop = time.perf_counter() - t_loop
         print('sequential loop: %d images in %.2f s = %.1f images/s file to file' % (n_img, t_loop, n_img / max(t_loop, 1e-9)))
     model.finish_half_guard()

@@ -10,7 +10,9 @@ Writes synthetic 512 x 512 hazy PNGs + a seeded checkpoint into a scratch direct
   sequential       python test.py --batchSize 8 (one batch at a time, encode on the main thread): the reference's loop; also with --nThreads T (decode in workers)
   pipelined        python test.py --batchSize 8 --in_flight 4 --nThreads T --writers W
   pipelined_procs  ... --nThreads T2 --writer_procs P (round 6: PNG encode in processes forked before the model exists, images through a shared-memory ring)
-both CLI runs with --precision half --u8_input --out_all (uint8 in, tensor2im bytes out of the tails' last launch), and checks that the two
+  pipelined_gpu_png  ... --in_flight 4 --nThreads T --writers W --gpu_png (PNG encode on the device, cfen_vit_dehazing_amd/png.py: the writers add the container and write);
+                   checked against the pipelined run for the same file names and pixels, with the ratio of the bytes written
+CLI_LEGS=a,b restricts the CLI runs to the named legs.  All CLI runs with --precision half --u8_input --out_all (uint8 in, tensor2im bytes out of the tails' last launch), and checks that the two
 result directories hold byte-identical files.  The GPU-only rate of the same batches is bench.py's headline; this tool says how much of it a
 file-to-file run sees and which stage is the bound.  Prints / writes ONE JSON object."""
 import json
@@ -83,7 +85,10 @@ def main():
         for tag, extra in (("sequential", ["--nThreads", "0"]), ("sequential_decode_in_workers", ["--nThreads", str(threads)]),
                            ("pipelined", ["--in_flight", "4", "--nThreads", str(threads), "--writers", str(writers)]),
                            ("pipelined_procs", ["--in_flight", "4", "--nThreads", str(threads2), "--writer_procs", str(procs)]),
-                           ("pipelined_procs_png_level_1", ["--in_flight", "4", "--nThreads", str(threads2), "--writer_procs", str(procs), "--png_compress_level", "1"])):
+                           ("pipelined_procs_png_level_1", ["--in_flight", "4", "--nThreads", str(threads2), "--writer_procs", str(procs), "--png_compress_level", "1"]),
+                           ("pipelined_gpu_png", ["--in_flight", "4", "--nThreads", str(threads), "--writers", str(writers), "--gpu_png"])):
+            if os.environ.get("CLI_LEGS") and tag not in os.environ["CLI_LEGS"].split(","):
+                continue
             t0 = time.perf_counter()
             p = subprocess.run([sys.executable, os.path.join(ROOT, "test.py")] + common + ["--results_dir", os.path.join(tmp, "res_" + tag)] + extra,
                                cwd=tmp, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -105,13 +110,20 @@ def main():
             res["png_level_1_same_pixels"] = sorted(os.listdir(lvl1)) == fa and all(
                 np.array_equal(np.asarray(Image.open(os.path.join(a, f))), np.asarray(Image.open(os.path.join(lvl1, f)))) for f in fa[::16])
             res["png_level_1_bytes_vs_default"] = round(sum(os.path.getsize(os.path.join(lvl1, f)) for f in fa) / max(1, sum(os.path.getsize(os.path.join(a, f)) for f in fa)), 3)
+        pipe_dir, gpu_dir = (os.path.join(tmp, "res_" + t, name, "test_32", "images") for t in ("pipelined", "pipelined_gpu_png"))
+        if os.path.isdir(pipe_dir) and os.path.isdir(gpu_dir):      # other bytes, the same pixels
+            fa = sorted(os.listdir(pipe_dir))
+            res["gpu_png_same_pixels"] = sorted(os.listdir(gpu_dir)) == fa and all(
+                np.array_equal(np.asarray(Image.open(os.path.join(pipe_dir, f))), np.asarray(Image.open(os.path.join(gpu_dir, f)))) for f in fa[::16])
+            res["gpu_png_bytes_vs_default"] = round(sum(os.path.getsize(os.path.join(gpu_dir, f)) for f in fa) / max(1, sum(os.path.getsize(os.path.join(pipe_dir, f)) for f in fa)), 3)
         for t in ("pipelined", "pipelined_procs", "sequential_decode_in_workers"):
             b = os.path.join(tmp, "res_" + t, name, "test_32", "images")
             if os.path.isdir(a) and os.path.isdir(b):
                 fa, fb = sorted(os.listdir(a)), sorted(os.listdir(b))
                 res["files_written"] = len(fb)
                 res["byte_identical_" + t] = fa == fb and all(open(os.path.join(a, f), "rb").read() == open(os.path.join(b, f), "rb").read() for f in fa)
-        res["byte_identical"] = all(v for k, v in res.items() if k.startswith("byte_identical_"))
+        if any(k.startswith("byte_identical_") for k in res):
+            res["byte_identical"] = all(v for k, v in res.items() if k.startswith("byte_identical_"))
         try:
             res["cpu_quota"] = open("/sys/fs/cgroup/cpu.max").read().strip()
         except OSError:
