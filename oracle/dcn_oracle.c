@@ -10,10 +10,14 @@
  * accumulated in double (the reference sums in a BLAS GEMM whose order is unspecified).
  *
  * PINNING: the reference extension cannot be built here (CUDA-only sources, THC headers, no nvcc) and
- * the reference ships no DCN tests or vectors, so this oracle is pinned only by the known-answer
- * properties that follow from the kernel code (tests/test_dcn_oracle.py): zero offsets == conv2d,
- * integer offsets == shifted-tap conv, mask == 1 == DCNv1 + bias, DeformConvPack at init == conv2d.
- * Against the reference implementation itself: parity unpinned.
+ * the reference ships no DCN tests or vectors.  tests/test_dcn_oracle.py pins this oracle (1) by the
+ * known-answer properties that follow from the kernel code: zero offsets == conv2d, integer offsets ==
+ * shifted-tap conv, mask == 1 == DCNv1 + bias, DeformConvPack at init == conv2d; (2) element by element
+ * against tests/dcn_ref.py, an independent float64 restatement of the operator's definition in plain
+ * torch: six geometries in which kH != kW, sH != sW, padH != padW, dilH != dilW all occur, groups and
+ * deformable groups cutting across each other, and samples exactly on the (-1, H) / (-1, W) bounds and
+ * 70 000 pixels off the image -- worst distance 2.7e-6.
+ * Against the reference's own binary: parity unpinned.
  *
  * Only tests/ and __graft_entry__.smoke() may load this library.
  */
@@ -103,7 +107,10 @@ int dcn_oracle_forward(const float* im, const float* offset, const float* mask, 
  * PINNING: as for the forward there is nothing of the reference to run; tests/test_dcn_oracle.py pins this against (1) torch autograd
  * of F.conv2d at zero offsets (grad_input, grad_weight, grad_bias), (2) central finite differences of dcn_oracle_forward in the offsets
  * and the mask (the analytic restatement of the reference's coordinate weights must agree with the numeric derivative of the restated
- * forward wherever the sample is differentiable), (3) linearity in grad_output.  Against the reference itself: parity unpinned. */
+ * forward wherever the sample is differentiable), (3) linearity in grad_output, (4) EVERY element of all five gradients against autograd
+ * of tests/dcn_ref.py (float64; nothing in it is hand-derived, so it shares no derivation with this file or the kernels) on the six
+ * h/w-distinct geometries named above, v1 and v2: worst distance 8.8e-6 where the largest gradient is 16.5.
+ * Against the reference's own binary: parity unpinned. */
 static void corner_weights(float h, float w, int H, int W, int* hl, int* wl, float wt[4], int ok[4]) {
   /* get_gradient_weight (.cu:116-142) for the four corners of (h, w): (hl, wl), (hl, wl+1), (hl+1, wl), (hl+1, wl+1); a corner outside
    * the image receives nothing (col2im's bounds test, .cu:316-317) */

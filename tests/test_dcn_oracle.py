@@ -1,6 +1,15 @@
-"""Pin the C oracle of the deformable conv (oracle/dcn_oracle.c) with the known-answer properties that
-follow from the reference kernel code: the reference ships no DCN tests or vectors and its
-CUDA extension cannot be built here, so these are the only pins (stated in the oracle's header)."""
+"""Pin the C oracle of the deformable conv (oracle/dcn_oracle.c): with the known-answer properties that
+follow from the reference kernel code, and element by element -- the output and all five
+gradients -- against tests/dcn_ref.py, a float64 restatement of the operator's definition whose gradients
+come from autograd (nothing in it is hand-derived, so it shares no code and no derivation with the oracle or
+the kernels).  The reference ships no DCN tests or vectors and its CUDA extension cannot be built here, so
+parity against the reference's own binary stays unpinned (stated in the oracle's header).
+
+Worst oracle <-> float64 max-abs distances measured over the six h/w-distinct geometries of GEOMETRIES, v1 and
+v2 (bar: 1e-5 x max(1, |want|max); each test prints its own):
+  output 2.7e-6, grad_input 2.0e-6, grad_offset 4.4e-6, grad_mask 3.1e-6, grad_weight 8.8e-6 (where |want|max
+  is 16.5: 5.4e-7 of it), grad_bias 5.7e-7; at the edge sample positions (forward only): output 1.5e-7.
+"""
 import math
 
 import pytest
@@ -8,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 import dcn_oracle
+import dcn_ref
 
 
 def rnd(shape, seed, scale=1.0):
@@ -140,3 +150,77 @@ def test_backward_is_linear_in_grad_output_and_accumulates_weight_grads():
         assert torch.allclose(c[k], 2 * a[k] - b[k], atol=1e-4), k
     half = dcn_oracle.deform_conv_backward(x, off, w, g1, 1, 1, 1, 1, 1, mask=mask, scale=0.5)
     assert torch.allclose(half["weight"], 0.5 * a["weight"], atol=1e-5)       # deform_conv_backward_parameters_cuda's `scale`
+
+
+# ---- the oracle against the float64 autograd restatement (tests/dcn_ref.py), every element ------------------------------------------------
+
+# (B, C, H, W, Cout, (kh, kw), (sh, sw), (ph, pw), (dh, dw), groups, deformable groups): every h / w pair differs somewhere
+GEOMETRIES = {
+    "1x3_s12_p01_d12_g2_dg2": (2, 8, 9, 11, 6, (1, 3), (1, 2), (0, 1), (1, 2), 2, 2),             # a row kernel
+    "3x1_s21_p10_d21_g1_dg3": (2, 6, 10, 8, 4, (3, 1), (2, 1), (1, 0), (2, 1), 1, 3),             # a column kernel
+    "3x2_s12_p21_g4_dg2_dg_spans_groups": (2, 8, 9, 12, 8, (3, 2), (1, 2), (2, 1), (1, 1), 4, 2),   # a deformable group of 4 channels over two conv groups of 2
+    "5x3_s21_p23_d12_g2_dg6_group_spans_dgs": (2, 12, 11, 9, 6, (5, 3), (2, 1), (2, 3), (1, 2), 2, 6),   # a conv group of 6 channels over three deformable groups of 2
+    "2x4_s13_p12_d31_g1_dg8": (3, 8, 8, 13, 4, (2, 4), (1, 3), (1, 2), (3, 1), 1, 8),
+    "3x3_s23_p02_d21_g1_dg1": (2, 4, 12, 10, 8, (3, 3), (2, 3), (0, 2), (2, 1), 1, 1),
+}
+BAR = 1e-5      # x max(1, |want|max): the tolerance of the known-answer pins above
+
+
+def _far(got, want):
+    """(max-abs distance, its bar)"""
+    return float((got.double() - want).abs().max()), BAR * max(1.0, float(want.abs().max()))
+
+
+@pytest.mark.parametrize("modulated", [False, True], ids=["v1", "v2"])
+@pytest.mark.parametrize("name", list(GEOMETRIES))
+def test_oracle_equals_float64_autograd_reference_on_every_element(name, modulated):
+    """output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias of loss = <output, grad_out>; sample positions kept 0.02 away from
+    integer coordinates for the gradients' sake (the bilinear sample has a kink there)"""
+    B, C, H, W, Cout, k, s, p, d, groups, dg = GEOMETRIES[name]
+    Ho, Wo = dcn_ref.out_size(H, W, k, s, p, d)
+    kk = k[0] * k[1]
+    x, w = rnd((B, C, H, W), 31), rnd((Cout, C // groups, k[0], k[1]), 32, 0.3)
+    off = dcn_ref.keep_off_integers(rnd((B, dg * 2 * kk, Ho, Wo), 33, 1.5))
+    mask = torch.rand(B, dg * kk, Ho, Wo, generator=torch.Generator().manual_seed(34)) if modulated else None
+    bias = rnd((Cout,), 35) if modulated else None
+    gy = rnd((B, Cout, Ho, Wo), 36)
+    leaves = {"input": x, "offset": off, "weight": w}
+    if modulated:
+        leaves.update(mask=mask, bias=bias)
+    leaves = {n: t.double().requires_grad_() for n, t in leaves.items()}
+    want = dcn_ref.deform_conv_f64(leaves["input"], leaves["offset"], leaves["weight"], s, p, d, groups, dg, mask=leaves.get("mask"), bias=leaves.get("bias"))
+    want.backward(gy.double())
+    got = dcn_oracle.deform_conv(x, off, w, s, p, d, groups, dg, mask=mask, bias=bias)
+    grads = dcn_oracle.deform_conv_backward(x, off, w, gy, s, p, d, groups, dg, mask=mask, with_bias=modulated)
+    assert got.shape == want.shape
+    report, failed = [], []
+    for what, g, r in [("output", got, want.detach())] + [("grad_" + n, grads[n], t.grad) for n, t in leaves.items()]:
+        dist, bar = _far(g, r)
+        report.append("%s %.2e (|want|max %.1f)" % (what, dist, float(r.abs().max())))
+        if not dist <= bar:
+            failed.append("%s: %.3e > %.1e" % (what, dist, bar))
+    print("oracle <-> float64 [%s %s]: %s" % (name, "v2" if modulated else "v1", ", ".join(report)))
+    assert not failed, failed
+
+
+@pytest.mark.parametrize("modulated", [False, True], ids=["v1", "v2"])
+@pytest.mark.parametrize("name", ["3x2_s12_p21_g4_dg2_dg_spans_groups", "3x3_s23_p02_d21_g1_dg1"])
+def test_oracle_equals_float64_reference_at_the_edge_sample_positions(name, modulated):
+    """forward only: samples exactly at -1, -0.5, 0, n - 1, n - 0.5 and n per axis, at integer positions, and 70 000 pixels off the image"""
+    B, C, H, W, Cout, k, s, p, d, groups, dg = GEOMETRIES[name]
+    Ho, Wo = dcn_ref.out_size(H, W, k, s, p, d)
+    kk = k[0] * k[1]
+    x, w = rnd((B, C, H, W), 41), rnd((Cout, C // groups, k[0], k[1]), 42, 0.3)
+    off = dcn_ref.edge_offsets(B, H, W, k, s, p, d, dg, far=70000).float()
+    rows, cols = dcn_ref.tap_base(H, W, k, s, p, d)
+    y = rows + off.double().view(B, dg, kk, 2, Ho, Wo)[:, :, :, 0]
+    for edge in (-1.0, -0.5, 0.0, H - 1.0, H - 0.5, float(H), -70000.0, 70000.0):
+        assert bool((y == edge).any()), "float32 offsets no longer put a sample at row %g" % edge
+    mask = torch.rand(B, dg * kk, Ho, Wo, generator=torch.Generator().manual_seed(44)) if modulated else None
+    bias = rnd((Cout,), 45) if modulated else None
+    want = dcn_ref.deform_conv_f64(x, off, w, s, p, d, groups, dg, mask=mask, bias=bias)
+    got = dcn_oracle.deform_conv(x, off, w, s, p, d, groups, dg, mask=mask, bias=bias)
+    dist, bar = _far(got, want)
+    print("oracle <-> float64 at the edges [%s %s]: output %.2e" % (name, "v2" if modulated else "v1", dist))
+    assert dist <= bar
+    assert float(want.abs().max()) > 0.1                       # not everything was sampled off the image
