@@ -103,6 +103,8 @@ SIGNATURES = {
     "cfen_tensor2im_u8": (_I, [_P, _P, _I, _I, _I, _P]),
     "cfen_tile_gather": (_I, [_I, _P, _P] + [_I] * 7 + [_P]),
     "cfen_tile_blend": (_I, [_I, _P] + [_I] * 8 + [_P, _P, _P, _P]),
+    "cfen_x8_expand": (_I, [_I, _P, _P, _I, _I, _I, _P]),
+    "cfen_x8_merge": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cfen_image_metrics_bytes": (c_size_t, [_I] * 4),
     "cfen_image_metrics": (_I, [_I, _P, _P] + [_I] * 4 + [c_float, c_float, _P, _P, _P]),
     "cfen_png_workspace_bytes": (c_size_t, [_I] * 3 + [ctypes.POINTER(c_size_t)] * 2),

@@ -303,6 +303,12 @@ int cfen_tile_blend(int dtype, const void* arena, int B, int T, int H, int W, in
                     void* stream) {
   return cfen_tile_blend_impl(dtype, arena, B, T, H, W, ny, nx, overlap, out_u8, xr, xs, xd, (hipStream_t)stream);
 }
+int cfen_x8_expand(int u8, const void* src, void* dst, int M, int m, int T, void* stream) {
+  return cfen_x8_expand_impl(u8, src, dst, M, m, T, (hipStream_t)stream);
+}
+int cfen_x8_merge(int dtype, const void* arena, int M, int T, int out_u8, void* xr, void* xs, void* xd, void* stream) {
+  return cfen_x8_merge_impl(dtype, arena, M, T, out_u8, xr, xs, xd, (hipStream_t)stream);
+}
 
 // cfen_tune / cfen_tune_query / cfen_tune_key: cfen_tune.cpp, from the table in cfen_tune_knobs.hpp
 

@@ -79,6 +79,9 @@ int cfen_png_deflate_impl(const unsigned char* images, int B, int H, int W, cons
 int cfen_tile_gather_impl(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, hipStream_t s);
 int cfen_tile_blend_impl(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs,
                          void* xd, hipStream_t s);
+// geometric self-ensemble (k_ensemble.hip)
+int cfen_x8_expand_impl(int u8, const void* src, void* dst, int M, int m, int T, hipStream_t s);
+int cfen_x8_merge_impl(int dtype, const void* arena, int M, int T, int out_u8, void* xr, void* xs, void* xd, hipStream_t s);
 int cfen_u8hwc_to_nhwc_impl(int dtype, const unsigned char* in, void* out, int B, int H, int W, int cs, hipStream_t s);
 int cfen_conv_impl(int dtype, const ConvDesc* d, hipStream_t s);
 // LDS-tiled stride-1 path (k_conv_tile.hip); weights in the "rows" layout, d->Kpad == cfen_conv_tile_kpad

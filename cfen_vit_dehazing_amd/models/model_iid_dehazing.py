@@ -86,8 +86,13 @@ class DECHLGVIT(BaseModel):
         self._tile = bool(getattr(opt, 'tile', False))
         self._eval = bool(getattr(opt, 'eval', False))
         self._metrics = {}
+        # --self_ensemble: every image (or tile) runs as its eight flips / transposes and the outputs are averaged (ensemble.py); like --tile outside the guard
+        self._x8 = bool(getattr(opt, 'self_ensemble', False))
         if self._tile and self._half_guard:
             print('notice: --precision half with --tile: the fp32 guard does not cover tiled images; they run in fp16 unchecked')
+            self._half_guard = False
+        if self._x8 and self._half_guard:
+            print('notice: --precision half with --self_ensemble: the fp32 guard does not cover ensemble images; they run in fp16 unchecked')
             self._half_guard = False
 
     # ---- --eval: PSNR / SSIM of the written bytes against the ground truth, on the device (metrics.py) ------------------------------------------------
@@ -216,9 +221,10 @@ class DECHLGVIT(BaseModel):
         if not self.actnorm_ready():
             return False           # the first REAL batch must initialise those layers (models/actnorm.py:25-37), not a dummy
         n = self.netG.cfg.image_size
-        if getattr(self, '_tile', False):
-            # the tiled path runs batches of up to --tile_batch tiles with float outputs (tiled.py): build that plan
-            batch_size = max(1, int(getattr(self.opt, 'tile_batch', 8)))
+        if getattr(self, '_tile', False) or getattr(self, '_x8', False):
+            # the tiled path runs batches of up to --tile_batch tiles with float outputs (tiled.py), the self-ensemble batches of the 8 variants of one
+            # image or tile with float outputs (ensemble.py): build that plan
+            batch_size = 8 if getattr(self, '_x8', False) else max(1, int(getattr(self.opt, 'tile_batch', 8)))
             x = torch.zeros((batch_size, n, n, 3) if u8_input else (batch_size, 3, n, n), dtype=torch.uint8 if u8_input else torch.float32, device=self.device)
             keep = self.netG.output_u8
             self.netG.output_u8 = False
@@ -261,10 +267,22 @@ class DECHLGVIT(BaseModel):
     def forward(self):
         j = self._batch_index
         self._batch_index = j + 1
+        x8 = getattr(self, '_x8', False)
+        if x8 and not self.actnorm_ready():
+            # forward_x8 refuses uninitialised ActNorm layers: one plain forward of the first batch initialises them, as the reference's first call would
+            self.netG.output_u8 = False
+            if getattr(self, '_tile', False):
+                self.netG.forward_tiled(self._net_in, overlap=getattr(self.opt, 'tile_overlap', None), tile_batch=getattr(self.opt, 'tile_batch', 8))
+            else:
+                self.netG(self._net_in)
         if getattr(self, '_tile', False):
             o = self.opt
             [self.fake_R, self.fake_S, self.fake_A] = self.netG.forward_tiled(self._net_in, overlap=getattr(o, 'tile_overlap', None),
-                                                                             tile_batch=getattr(o, 'tile_batch', 8), output_u8=getattr(self, '_u8_out', False))
+                                                                             tile_batch=getattr(o, 'tile_batch', 8), output_u8=getattr(self, '_u8_out', False),
+                                                                             **({'self_ensemble': True} if x8 else {}))
+            return
+        if x8:
+            [self.fake_R, self.fake_S, self.fake_A] = self.netG.forward_x8(self._net_in, output_u8=getattr(self, '_u8_out', False))
             return
         if self.guard_due(j):
             self.netG.output_u8 = False                   # the guard compares the float outputs

@@ -417,6 +417,51 @@ def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False):
     return outs
 
 
+def x8_expand(images, m=0, out=None):
+    """cfen_x8_expand: the eight flips / transposes of image `m` of `images` -- (M,T,T,3) uint8 or (M,3,T,T) fp32 CUDA tensor -- as the network's
+    batch-8 input slab, (8,T,T,3) uint8 or (8,3,T,T) fp32 (`out`, else allocated), in the variant order of ensemble.py"""
+    _cuda(images, out)
+    u8 = images.dtype == torch.uint8
+    if images.dim() != 4 or not images.is_contiguous() or (u8 and images.shape[3] != 3) or \
+            (not u8 and (images.dtype != torch.float32 or images.shape[1] != 3)) or images.shape[1 if u8 else 2] != images.shape[2 if u8 else 3]:
+        raise ValueError("x8_expand needs contiguous (M,T,T,3) uint8 or (M,3,T,T) float32 square images, got %s %s" % (tuple(images.shape), images.dtype))
+    M, T = images.shape[0], images.shape[2]
+    shape = (8, T, T, 3) if u8 else (8, 3, T, T)
+    if out is None:
+        out = torch.empty(shape, dtype=images.dtype, device=images.device)
+    elif tuple(out.shape) != shape or out.dtype != images.dtype or not out.is_contiguous():
+        raise ValueError("x8_expand: out must be a contiguous %s tensor of shape %s" % (images.dtype, shape))
+    check(_lib.load().cfen_x8_expand(int(u8), ptr(images), ptr(out), M, int(m), T, current_stream()), "x8_expand")
+    return out
+
+
+def x8_merge(arena, M, T, output_u8=False, out=None):
+    """cfen_x8_merge: `arena` holds M forward output slabs back to back, float32 or float16, slab m = [xr (8,3,T,T) | xs (8,1,T,T) | xd (8,3,T,T)] of
+    the eight variants of image m; returns the ensemble [xr (M,3,T,T), xs (M,1,T,T), xd (M,3,T,T)] float32 -- each variant mapped back, summed in
+    fp32 in variant order, times 1/8 -- or with output_u8 three (M,T,T,3) uint8 images (util.tensor2im's bytes of those values).  `out`: optional flat
+    float32 buffer of 7*M*T*T elements that receives [xr | xs | xd] back to back, as forward(x, out=) lays them out; the results are views of it"""
+    _cuda(arena, out)
+    need = M * 56 * T * T
+    if arena.dtype not in (torch.float32, torch.float16) or arena.dim() != 1 or not arena.is_contiguous() or arena.numel() < need:
+        raise ValueError("x8_merge: the arena must be a flat tensor of %d float32 / float16 elements (%d slabs of 7*8*%d*%d), got %s %s"
+                         % (need, M, T, T, tuple(arena.shape), arena.dtype))
+    dev = arena.device
+    px = M * T * T
+    if output_u8:
+        if out is not None:
+            raise ValueError("x8_merge: output_u8 allocates its own (M,T,T,3) uint8 outputs: no `out` buffer")
+        outs = [torch.empty(M, T, T, 3, dtype=torch.uint8, device=dev) for _ in range(3)]
+    elif out is not None:
+        if out.dtype != torch.float32 or out.dim() != 1 or out.numel() != 7 * px or not out.is_contiguous() or out.device != dev:
+            raise ValueError("x8_merge: out must be a flat contiguous float32 buffer of 7*M*T*T = %d elements on the arena's device" % (7 * px))
+        outs = [out[:3 * px].view(M, 3, T, T), out[3 * px:4 * px].view(M, 1, T, T), out[4 * px:].view(M, 3, T, T)]
+    else:
+        outs = [torch.empty(M, c, T, T, dtype=torch.float32, device=dev) for c in (3, 1, 3)]
+    check(_lib.load().cfen_x8_merge(dtype_code(arena.dtype), ptr(arena), M, T, int(output_u8), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]),
+                                    current_stream()), "x8_merge")
+    return outs
+
+
 def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     """cfen_image_metrics: per image pair (sse, ssim) as two float64 CUDA tensors of shape (B,), in one fused pass.
 

@@ -88,6 +88,11 @@ class BaseOptions():
                             'back to the input size (cfen_vit_dehazing_amd/tiled.py); needs --batchSize 1 and --in_flight 1')
         p.add_argument('--tile_overlap', type=int, default=None, help='(extension) --tile: overlap of neighbouring tiles in pixels (default image_size // 8)')
         p.add_argument('--tile_batch', type=int, default=8, help='(extension) --tile: tiles per forward')
+        p.add_argument('--self_ensemble', action='store_true',
+                       help='(extension; the reference accepts the flag, base_options.py:133, and never acts on it) geometric self-ensemble: every image '
+                            'runs as its eight flips / transposes in one batch-8 forward and the outputs, mapped back, are averaged on the device '
+                            '(cfen_vit_dehazing_amd/ensemble.py; the reference\'s Model.forward_x8, models/vit_model.py:102-147); 8x the forward time; '
+                            'needs --in_flight 1')
         p.add_argument('--eval', action='store_true',
                        help='(extension) score every dehazed image against its ground truth on the device: per-image PSNR (RGB, 10 log10(1 / MSE)) and SSIM '
                             '(the reference\'s pytorch_msssim.ssim, 11 x 11 Gaussian window, valid convolution) of the very bytes written to the PNG, into '
@@ -135,6 +140,9 @@ class BaseOptions():
                                  '(got --batchSize %d --in_flight %d)' % (opt.batchSize, opt.in_flight))
             if opt.tile_batch < 1:
                 raise ValueError('--tile_batch must be >= 1')
+        if getattr(opt, 'self_ensemble', False) and opt.in_flight != 1:
+            raise ValueError('--self_ensemble runs through the sequential loop: it needs --in_flight 1 (got --in_flight %d); the pipelined driver '
+                             'replays plain forwards only' % opt.in_flight)
         if getattr(opt, 'eval', False):
             if opt.in_flight != 1:
                 raise ValueError('--eval scores the images of the sequential loop: it needs --in_flight 1 (got --in_flight %d); the pipelined driver '
@@ -160,6 +168,8 @@ class BaseOptions():
             args = {k: v for k, v in args.items() if k not in ('eval', 'gt_dir')}      # a run without --eval prints and records what it always did
         if not getattr(opt, 'gpu_png', False):
             args = {k: v for k, v in args.items() if k != 'gpu_png'}                   # ... and so does one without --gpu_png
+        if not getattr(opt, 'self_ensemble', False):
+            args = {k: v for k, v in args.items() if k != 'self_ensemble'}             # ... and one without --self_ensemble
         if opt.dist_rank == 0:
             print('------------ Options -------------')
             for k, v in sorted(args.items()):

@@ -14,7 +14,7 @@ Tile plan, per axis of extent L, overlap o (0 <= o <= T/2, default T // 8):
 """
 import torch
 
-from . import ops
+from . import ensemble, ops
 
 MAX_ARENA_BYTES = 8 << 30
 
@@ -46,14 +46,15 @@ def tile_grid(H, W, T, overlap):
     return tile_origins(H, T, tile_count(H, T, overlap)), tile_origins(W, T, tile_count(W, T, overlap))
 
 
-def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=MAX_ARENA_BYTES):
+def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=MAX_ARENA_BYTES, self_ensemble=False):
     """[xr, xs, xd] of an image of any size through `net` (a hipnet.dec_ipt) as overlapping T x T tiles.
 
     image: (H,W,3) uint8 or (3,H,W) float32 in [-1,1] CUDA tensor; a leading batch dimension of 1 is accepted and kept on the outputs.
     Returns float32 xr (3,H,W), xs (1,H,W), xd (3,H,W), or with output_u8 three (H,W,3) uint8 images (util.tensor2im's bytes, produced by the
     blend from the float values).  Tiles run tile_batch at a time (the last batch padded with copies of the last tile); a net whose ActNorm layers
     are still uninitialised initialises them from the first tile batch, as its first plain forward would.  An image whose single-tile plan covers
-    it (H = W = T) comes out bitwise as the plain forward's."""
+    it (H = W = T) comes out bitwise as the plain forward's.  self_ensemble: every tile batch goes through the geometric self-ensemble
+    (ensemble.dehaze_x8: eight forwards per tile) into a float32 arena, the blend is the same; the ActNorm layers must be initialised then."""
     if not isinstance(image, torch.Tensor) or not image.is_cuda:
         raise ValueError("dehaze_tiled needs a CUDA tensor image; there is no CPU fallback")
     batched = image.dim() == 4
@@ -75,7 +76,7 @@ def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_ar
         raise ValueError("tile_batch must be >= 1")
     B = min(int(tile_batch), ntiles)
     nslabs = -(-ntiles // B)
-    odt = torch.float16 if net.output_f16 else torch.float32
+    odt = torch.float16 if net.output_f16 and not self_ensemble else torch.float32
     slab = 7 * B * T * T
     arena_bytes = nslabs * slab * (2 if odt == torch.float16 else 4)
     if arena_bytes > max_arena_bytes:
@@ -88,7 +89,10 @@ def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_ar
     try:
         for s in range(nslabs):
             ops.tile_gather(image, T, ny, nx, s * B, B, out=slab_in)
-            net(slab_in, out=arena[s * slab:(s + 1) * slab])
+            if self_ensemble:
+                ensemble.dehaze_x8(net, slab_in, out=arena[s * slab:(s + 1) * slab])
+            else:
+                net(slab_in, out=arena[s * slab:(s + 1) * slab])
     finally:
         net.output_u8 = keep_u8
     outs = ops.tile_blend(arena, B, T, H, W, ny, nx, o, output_u8=output_u8)

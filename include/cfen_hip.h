@@ -289,6 +289,20 @@ int cfen_tile_gather(int u8, const void* src, void* dst, int H, int W, int T, in
 int cfen_tile_blend(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs, void* xd,
                     void* stream);
 
+/* Geometric self-ensemble (x8) of the generator (ensemble.py; the reference's Model.forward_x8, models/vit_model.py:102-147): the output is the
+ * mean over the eight flips / transposes of the input.  With v = flip W, h = flip H, t = swap H and W, variant i = b0 + 2 b1 + 4 b2 of a T x T
+ * plane x is x_i = t^b2(h^b1(v^b0(x))) (v applied first); every output plane y_i of the forward of x_i is mapped back as v^b0(h^b1(t^b2(y_i))) and
+ * the result is the fp32 sum of the eight in increasing i, times 0.125f -- no other arithmetic, no atomics: bitwise reproducible.
+ *
+ * expand: image m of the M images at src into the network's batch-8 input slab dst, in variant order.  A pure copy.
+ *   u8 = 1: src (M,T,T,3) uint8 -> dst (8,T,T,3) uint8;  u8 = 0: src (M,3,T,T) fp32 -> dst (8,3,T,T) fp32.
+ * merge: M forward output slabs back to back, dtype 0 fp32 / 1 fp16; slab m = [xr (8,3,T,T) | xs (8,1,T,T) | xd (8,3,T,T)] (56 T T elements) of
+ *   the eight variants of image m.  out_u8 = 0: xr (M,3,T,T), xs (M,1,T,T), xd (M,3,T,T) fp32.  out_u8 = 1: xr / xs / xd each (M,T,T,3) uint8,
+ *   tensor2im's arithmetic of the fp32 value ((x+1)/2*255 truncated, xs tiled to 3 channels; util/util.py:12-24).
+ * T % 16 == 0, 16 <= T <= 8192; 1 <= M <= 4096; every pointer 16-byte aligned.                                                                   */
+int cfen_x8_expand(int u8, const void* src, void* dst, int M, int m, int T, void* stream);
+int cfen_x8_merge(int dtype, const void* arena, int M, int T, int out_u8, void* xr, void* xs, void* xd, void* stream);
+
 /* Image quality of an output against its ground truth, per image pair, in one fused pass (csrc/k_metrics.hip; metrics.py, test.py --eval).
  * Both images are scored on the [0,1] scale in fp32, data range L = 1:
  *   u8 = 1: a, b (B,H,W,3) uint8, v -> v / 255 (C must be 3);  u8 = 0: a, b (B,C,H,W) fp32, C 1 or 3, v -> (v - lo) / (hi - lo), e.g. (-1, 1)
