@@ -107,6 +107,8 @@ SIGNATURES = {
     "cfen_x8_merge": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cfen_image_metrics_bytes": (c_size_t, [_I] * 4),
     "cfen_image_metrics": (_I, [_I, _P, _P] + [_I] * 4 + [c_float, c_float, _P, _P, _P]),
+    "cfen_image_msssim_bytes": (c_size_t, [_I] * 4),
+    "cfen_image_msssim": (_I, [_I, _P, _P] + [_I] * 4 + [c_float, c_float, _P, _P, _P]),
     "cfen_png_workspace_bytes": (c_size_t, [_I] * 3 + [ctypes.POINTER(c_size_t)] * 2),
     "cfen_png_deflate": (_I, [_P] + [_I] * 3 + [_P, _I, _P, _P, _P, _P]),
     "cfen_embed_qkv": (_I, [_I, ctypes.POINTER(EmbedQkvArgsC), _P]),

@@ -289,6 +289,11 @@ int cfen_image_metrics(int u8, const void* a, const void* b, int B, int C, int H
                        void* stream) {
   return cfen_image_metrics_impl(u8, a, b, B, C, H, W, lo, hi, scratch, out, (hipStream_t)stream);
 }
+size_t cfen_image_msssim_bytes(int B, int C, int H, int W) { return cfen_image_msssim_bytes_impl(B, C, H, W); }
+int cfen_image_msssim(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
+                      void* stream) {
+  return cfen_image_msssim_impl(u8, a, b, B, C, H, W, lo, hi, scratch, out, (hipStream_t)stream);
+}
 size_t cfen_png_workspace_bytes(int B, int H, int W, size_t* strip_bytes, size_t* out_stride) {
   return cfen_png_workspace_bytes_impl(B, H, W, strip_bytes, out_stride);
 }

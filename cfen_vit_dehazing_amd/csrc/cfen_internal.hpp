@@ -73,6 +73,9 @@ int cfen_tensor2im_u8_impl(const float* in, unsigned char* out, int C, int H, in
 size_t cfen_image_metrics_bytes_impl(int B, int C, int H, int W);
 int cfen_image_metrics_impl(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
                             hipStream_t s);
+size_t cfen_image_msssim_bytes_impl(int B, int C, int H, int W);
+int cfen_image_msssim_impl(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
+                           hipStream_t s);
 size_t cfen_png_workspace_bytes_impl(int B, int H, int W, size_t* strip_bytes, size_t* out_stride);
 int cfen_png_deflate_impl(const unsigned char* images, int B, int H, int W, const void* tables, int n_tables, void* workspace, unsigned char* out,
                           int* out_lengths, hipStream_t s);

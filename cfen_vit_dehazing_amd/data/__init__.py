@@ -82,6 +82,17 @@ def pair_ground_truth(hazy_paths, gt_dir):
     return pairs
 
 
+def check_msssim_sizes(pairs, min_edge):
+    """--eval_metrics ...,msssim: ValueError naming the first hazy image whose ground truth (the size its output is scored at) is under min_edge
+    pixels on a side; only the files' headers are read.  Raised when the dataset is built, before any forward."""
+    for hazy, gt in pairs.items():
+        with Image.open(gt) as im:
+            W, H = im.size
+        if min(H, W) < min_edge:
+            raise ValueError("--eval_metrics msssim: %s is scored at %d x %d (%s); MS-SSIM over five levels needs at least %d pixels on a side"
+                             % (hazy, H, W, gt, min_edge))
+
+
 class DECVITDATA(torch.utils.data.Dataset):
     def initialize(self, opt):
         self.opt = opt
@@ -103,6 +114,9 @@ class DECVITDATA(torch.utils.data.Dataset):
         self.transform = get_transform(opt)
         # --eval: every hazy image needs its ground truth (the reference's training-mode folder `clear`, data/dec_vit_data.py:20), found now
         self.A_of = pair_ground_truth(self.B_paths, getattr(opt, 'gt_dir', None) or os.path.join(opt.dataroot, 'clear')) if getattr(opt, 'eval', False) else None
+        if self.A_of is not None and 'msssim' in (getattr(opt, 'eval_metrics', None) or '').split(','):
+            from ..metrics import MSSSIM_MIN_EDGE
+            check_msssim_sizes(self.A_of, MSSSIM_MIN_EDGE)
 
     def __getitem__(self, index):
         if self.opt.sb:

@@ -5,12 +5,18 @@ Definition (fixed; include/cfen_hip.h has the long form).  Both images are score
         11 x 11 Gaussian window (sigma 1.5), valid convolution, C1 = 0.01^2, C2 = 0.03^2, the mean over the 3 channels and all window positions.
   PSNR  10 log10(1 / MSE), the MSE over all 3 H W values; inf for equal images.  The reference has no PSNR code: this is the standard
         definition, taken over the RGB values -- NOT over the Y channel of YCbCr some dehazing papers report.
-Images under 11 x 11 are refused: the reference shrinks its window there, this project does not follow it.
+  MS-SSIM  the reference's pytorch_msssim.msssim(window_size=11, size_average=True, val_range=1, normalize=None) (pytorch_msssim/__init__.py:73-107):
+        five levels of 2 x 2 means, at each the mean SSIM and the mean cs = (2 sigma12 + C2) / (sigma1^2 + sigma2^2 + C2) from the device
+        (ops.image_msssim), then prod_{l<4} cs_l^w_l * ssim_4^w_4 here in float64; NaN when one of those five terms is negative, as in the reference.
+Images under 11 x 11 (MS-SSIM: under 176 x 176) are refused: the reference shrinks its window there, this project does not follow it.
 
 CUDA tensors only; there is no CPU fallback.  `format_csv` / `summarize` are the text side of test.py --eval."""
 import math
 
 CSV_HEADER = "image,psnr,ssim"
+COLUMNS = ("psnr", "ssim", "msssim")                                 # what --eval_metrics may name, in the order of the csv
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MSSSIM_MIN_EDGE = 176                                                # 11 * 2^4: the fifth level still holds one window
 
 
 def psnr_from_sse(sse, n_values):
@@ -33,8 +39,50 @@ def psnr_ssim(out, gt, value_range=(-1.0, 1.0)):
     return [(psnr_from_sse(s, n), float(m)) for s, m in both]
 
 
+def msssim_from_levels(levels):
+    """MS-SSIM per image from the level values (ssim_l, cs_l): levels (B,5,2) or (5,2), a tensor (copied to the host), array or nested list.  Float64
+    on the host: cs_0^w_0 cs_1^w_1 cs_2^w_2 cs_3^w_3 ssim_4^w_4, NaN when one of these five terms is negative or NaN.  A list of B floats (one float
+    for a (5,2) input)."""
+    if hasattr(levels, "detach"):
+        levels = levels.detach().cpu()
+    levels = levels.tolist() if hasattr(levels, "tolist") else levels
+    single = len(levels) == 5 and not hasattr(levels[0][0], "__len__")
+    res = []
+    for lv in ([levels] if single else levels):
+        if len(lv) != 5 or any(len(pair) != 2 for pair in lv):
+            raise ValueError("msssim_from_levels: five (ssim, cs) pairs per image, got %r" % (lv,))
+        terms = [float(lv[l][1]) for l in range(4)] + [float(lv[4][0])]
+        res.append(float("nan") if any(not t >= 0 for t in terms) else math.prod(t ** w for t, w in zip(terms, MSSSIM_WEIGHTS)))
+    return res[0] if single else res
+
+
+def psnr_ssim_msssim(out, gt, value_range=(-1.0, 1.0)):
+    """[(psnr, ssim, msssim), ...] per image, Python floats; psnr and ssim are exactly psnr_ssim's.  Inputs as for psnr_ssim, min(H, W) >= 176.  One
+    device call (six launches) and one copy of 88 B bytes back."""
+    import torch
+    from . import ops
+    if not isinstance(out, torch.Tensor) or not isinstance(gt, torch.Tensor) or not out.is_cuda or not gt.is_cuda:
+        raise ValueError("psnr_ssim_msssim needs CUDA tensors; there is no CPU fallback")
+    buf = torch.empty(out.shape[0] if out.dim() == 4 else 1, 11, dtype=torch.float64, device=out.device)
+    sse, levels = ops.image_msssim(out.contiguous(), gt.contiguous(), value_range=value_range, out=buf)
+    n = out.numel() // sse.numel()
+    host = buf.cpu().tolist()
+    return [(psnr_from_sse(r[0], n), float(r[1]), msssim_from_levels([r[1 + 2 * l:3 + 2 * l] for l in range(5)])) for r in host]
+
+
+def parse_columns(text):
+    """--eval_metrics: 'psnr,ssim' or 'psnr,ssim,msssim' -> the tuple of columns; psnr and ssim are always written, in the csv's fixed order"""
+    names = [t.strip() for t in str(text).split(",") if t.strip()]
+    for n in names:
+        if n not in COLUMNS:
+            raise ValueError("--eval_metrics: unknown metric '%s' (known: %s)" % (n, ", ".join(COLUMNS)))
+    if len(set(names)) != len(names) or "psnr" not in names or "ssim" not in names:
+        raise ValueError("--eval_metrics: psnr and ssim are always written, each name once: psnr,ssim or psnr,ssim,msssim (got '%s')" % text)
+    return tuple(c for c in COLUMNS if c in names)
+
+
 def _fmt(v):
-    return "inf" if math.isinf(v) else "%.6f" % v
+    return "inf" if math.isinf(v) else "nan" if math.isnan(v) else "%.6f" % v
 
 
 def format_csv(rows):
@@ -55,3 +103,39 @@ def summary_line(rows):
     s = summarize(rows)
     return "eval: %d images, mean PSNR %.4f dB over %d finite (%d infinite), mean SSIM %.6f" % (
         s["images"], s["psnr_mean"], s["images"] - s["psnr_infinite"], s["psnr_infinite"], s["ssim_mean"])
+
+
+# ---- the same three with the column list (--eval_metrics): rows are (image, value per column ...) ---------------------------------------------------
+def csv_header(columns):
+    return ",".join(("image",) + tuple(columns))
+
+
+def format_csv_columns(rows, columns):
+    """the text of metrics.csv for the given columns: %.6f, an infinite PSNR as `inf`, an undefined MS-SSIM as `nan`; for ('psnr', 'ssim') it is
+    format_csv's text"""
+    for r in rows:
+        if len(r) != 1 + len(columns):
+            raise ValueError("format_csv_columns: a row of %d values for the columns %s" % (len(r) - 1, ",".join(columns)))
+    return "".join([csv_header(columns) + "\n"] + [",".join([str(r[0])] + [_fmt(v) for v in r[1:]]) + "\n" for r in rows])
+
+
+def summarize_columns(rows, columns):
+    """summarize() of the psnr and ssim columns, plus with 'msssim': 'msssim_mean' (over the rows that are not NaN, nan when there is none) and
+    'msssim_nan' (how many are NaN)"""
+    ip, iss = 1 + list(columns).index("psnr"), 1 + list(columns).index("ssim")
+    s = summarize([(r[0], r[ip], r[iss]) for r in rows])
+    if "msssim" in columns:
+        im = 1 + list(columns).index("msssim")
+        good = [r[im] for r in rows if not math.isnan(r[im])]
+        s["msssim_mean"] = sum(good) / len(good) if good else float("nan")
+        s["msssim_nan"] = len(rows) - len(good)
+    return s
+
+
+def summary_line_columns(rows, columns):
+    ip, iss = 1 + list(columns).index("psnr"), 1 + list(columns).index("ssim")
+    line = summary_line([(r[0], r[ip], r[iss]) for r in rows])
+    if "msssim" in columns:
+        s = summarize_columns(rows, columns)
+        line += ", mean MS-SSIM %.6f over %d (%d nan)" % (s["msssim_mean"], s["images"] - s["msssim_nan"], s["msssim_nan"])
+    return line

@@ -86,6 +86,7 @@ class DECHLGVIT(BaseModel):
         self._tile = bool(getattr(opt, 'tile', False))
         self._eval = bool(getattr(opt, 'eval', False))
         self._metrics = {}
+        self._eval_msssim = self._eval and 'msssim' in (getattr(opt, 'eval_metrics', None) or '').split(',')      # --eval_metrics psnr,ssim,msssim
         # --self_ensemble: every image (or tile) runs as its eight flips / transposes and the outputs are averaged (ensemble.py); like --tile outside the guard
         self._x8 = bool(getattr(opt, 'self_ensemble', False))
         if self._tile and self._half_guard:
@@ -113,12 +114,17 @@ class DECHLGVIT(BaseModel):
         if tuple(out.shape) != tuple(gt.shape):
             raise ValueError('--eval: the ground truth %s is %d x %d but the output for %s is %d x %d'
                              % (self._gt_paths[0], gt.shape[1], gt.shape[2], self.image_paths[0], out.shape[1], out.shape[2]))
+        if getattr(self, '_eval_msssim', False):
+            for path, row in zip(self.image_paths, metrics.psnr_ssim_msssim(out, gt)):
+                self._metrics[path] = row          # (psnr, ssim, msssim): the one device call serves the whole row
+            return
         for path, (p, s) in zip(self.image_paths, metrics.psnr_ssim(out, gt)):
             self._metrics[path] = (p, s)           # an image run again (redone in fp32 after a failed half guard) replaces its row, in place
 
     def current_metrics(self):
-        """[(hazy image path, psnr, ssim), ...] of every image scored so far, in the order they first ran"""
-        return [(path, p, s) for path, (p, s) in getattr(self, '_metrics', {}).items()]
+        """[(hazy image path, psnr, ssim), ...] of every image scored so far, in the order they first ran; with --eval_metrics psnr,ssim,msssim
+        the rows are (hazy image path, psnr, ssim, msssim)"""
+        return [(path,) + tuple(row) for path, row in getattr(self, '_metrics', {}).items()]
 
     def _guard_dir(self):
         import os

@@ -490,6 +490,34 @@ def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     return out[:, 0], out[:, 1]      # (scratch goes back to torch's allocator on the stream it was used on)
 
 
+def image_msssim(a, b, value_range=(-1.0, 1.0), out=None):
+    """cfen_image_msssim: per image pair (sse, levels): sse a float64 CUDA tensor of shape (B,), levels a (B,5,2) float64 CUDA tensor of
+    (ssim_l, cs_l) over the five levels of the 2 x 2 mean pyramid -- the reference's pytorch_msssim.msssim(window_size=11, val_range=1,
+    normalize=None) up to the final powers and product, which metrics.msssim_from_levels takes on the host in float64.
+
+    a, b, value_range: as for image_metrics; min(H, W) >= 176.  sse and levels[:, 0, 0] are bitwise what image_metrics returns for the same input.
+    out: a contiguous (B, 11) float64 CUDA tensor to write into (sse, then the ten level values); the results are views of it."""
+    _cuda(a, b)
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
+        raise ValueError("image_msssim: the two images differ in shape, dtype or device: %s %s against %s %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    u8 = a.dtype == torch.uint8
+    if a.dim() != 4 or (u8 and a.shape[3] != 3) or (not u8 and (a.dtype != torch.float32 or a.shape[1] not in (1, 3))):
+        raise ValueError("image_msssim needs (B,H,W,3) uint8 or (B,1|3,H,W) float32 images, got %s %s" % (tuple(a.shape), a.dtype))
+    B, C, H, W = (a.shape[0], 3, a.shape[1], a.shape[2]) if u8 else tuple(a.shape)
+    lib = _lib.load()
+    nbytes = lib.cfen_image_msssim_bytes(B, C, H, W)
+    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=a.device)
+    if out is None:
+        out = torch.empty(B, 11, dtype=torch.float64, device=a.device)
+    elif tuple(out.shape) != (B, 11) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("image_msssim: out must be a contiguous (%d, 11) float64 CUDA tensor" % B)
+    lo, hi = value_range
+    check(lib.cfen_image_msssim(int(u8), ptr(a), ptr(b), B, C, H, W, float(lo), float(hi), ptr(scratch), ptr(out), current_stream()), "image_msssim")
+    return out[:, 0], out[:, 1:].unflatten(1, (5, 2))
+
+
 def png_deflate(images, out=None, out_lengths=None):
     """cfen_png_deflate: contiguous (B,H,W,3) uint8 CUDA images -> (slab, lengths): slab (B, out_stride) uint8 holds image b's finished zlib
     stream (the IDAT payload of an 8-bit RGB PNG, png.assemble adds the container) in slab[b, :lengths[b]]; lengths (B,) int32.  The candidate

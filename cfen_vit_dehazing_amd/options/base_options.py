@@ -97,6 +97,10 @@ class BaseOptions():
                        help='(extension) score every dehazed image against its ground truth on the device: per-image PSNR (RGB, 10 log10(1 / MSE)) and SSIM '
                             '(the reference\'s pytorch_msssim.ssim, 11 x 11 Gaussian window, valid convolution) of the very bytes written to the PNG, into '
                             'results/<name>/<phase>_<epoch>/metrics.csv; needs --sb and --in_flight 1')
+        p.add_argument('--eval_metrics', type=str, default=None,
+                       help='(extension) --eval: the columns of metrics.csv, psnr,ssim (default) or psnr,ssim,msssim. msssim is the reference\'s '
+                            'pytorch_msssim.msssim (five levels of 2 x 2 means, normalize=None: nan where a level is anticorrelated), scored on the device '
+                            'in the same call; every image must be at least 176 pixels on a side')
         p.add_argument('--gt_dir', type=str, default=None,
                        help='(extension) --eval: folder of ground-truth images, paired by stem or by the stem up to its first "_" (default <dataroot>/clear)')
         p.add_argument('--patch_dim', type=int, default=2)
@@ -150,6 +154,11 @@ class BaseOptions():
             if not opt.sb:
                 raise ValueError('--eval needs --sb: without it the images are sampled randomly (dec_vit_data.py:51-58) and metrics.csv would not '
                                  'cover the dataset in order')
+        eval_metrics_given = getattr(opt, 'eval_metrics', None) is not None
+        if eval_metrics_given and not getattr(opt, 'eval', False):
+            raise ValueError('--eval_metrics names the columns of --eval\'s metrics.csv: it needs --eval')
+        from .. import metrics as _metrics
+        opt.eval_metrics = ','.join(_metrics.parse_columns(opt.eval_metrics if eval_metrics_given else 'psnr,ssim'))
         if not -1 <= opt.png_compress_level <= 9:
             raise ValueError('--png_compress_level must be -1 (PIL default) or 0..9')
         from .. import png as _png
@@ -166,6 +175,8 @@ class BaseOptions():
         args = vars(opt)
         if not getattr(opt, 'eval', False):
             args = {k: v for k, v in args.items() if k not in ('eval', 'gt_dir')}      # a run without --eval prints and records what it always did
+        if not eval_metrics_given:
+            args = {k: v for k, v in args.items() if k != 'eval_metrics'}              # ... and one without --eval_metrics, with --eval or not
         if not getattr(opt, 'gpu_png', False):
             args = {k: v for k, v in args.items() if k != 'gpu_png'}                   # ... and so does one without --gpu_png
         if not getattr(opt, 'self_ensemble', False):

@@ -320,6 +320,30 @@ size_t cfen_image_metrics_bytes(int B, int C, int H, int W);
 int cfen_image_metrics(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
                        void* stream);
 
+/* Multi-scale SSIM of the same image pairs (csrc/k_metrics.hip; metrics.py, test.py --eval --eval_metrics psnr,ssim,msssim): the reference's
+ * pytorch_msssim.msssim(img1, img2, window_size = 11, size_average = True, val_range = 1, normalize = None) (pytorch_msssim/__init__.py:73-107).
+ * Inputs, u8, lo / hi and the [0,1] mapping are those of cfen_image_metrics.
+ *   Pyramid: level 0 is the mapped image.  Level l + 1 is F.avg_pool2d(level l, (2, 2)): the mean of each 2 x 2 block in fp32,
+ *            (((a + b) + c) + d) * 0.25f with a, b the upper and c, d the lower pair.  Odd sizes floor: H_{l+1} = H_l / 2, W_{l+1} = W_l / 2 in
+ *            integers, the last row / column is dropped.  Both images are pooled.
+ *   Levels : at each of the five levels the same 11 x 11 Gaussian window (sigma 1.5, normalised) as a VALID convolution, C1 = 0.01^2, C2 = 0.03^2,
+ *            and two means over all C (H_l - 10) (W_l - 10) window positions:
+ *              ssim_l  the mean of the SSIM map of cfen_image_metrics,
+ *              cs_l    the mean of (2 sigma12 + C2) / (sigma1^2 + sigma2^2 + C2).
+ *   Value  : MS-SSIM = cs_0^w_0 cs_1^w_1 cs_2^w_2 cs_3^w_3 ssim_4^w_4, w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333).  The device returns the
+ *            ten level values; the powers and the product are the caller's, in float64 (metrics.msssim_from_levels).  With normalize = None the
+ *            reference gives NaN when one of the five terms it uses is negative, and so does metrics.py.
+ *   Size   : level 4 must hold one window, so min(H, W) >= 176 = 11 * 2^4.  The reference shrinks its window for smaller images; this library
+ *            refuses them (CFEN_ERR_ARG, the message names 176).
+ * out: [B][11] doubles on the device, 8-byte aligned: SSE, then (ssim_l, cs_l) for l = 0 .. 4.  out[b][0] and out[b][1] are bit for bit what
+ * cfen_image_metrics writes for the same input, so one call serves PSNR, SSIM and MS-SSIM.  scratch: cfen_image_msssim_bytes(B, C, H, W) bytes of
+ * device memory, 8-byte aligned, contents irrelevant before and after (per workgroup tile of every level one (SSE, SSIM sum, cs sum) triple, then
+ * levels 1 .. 4 of both images as planar fp32; 0 for dimensions the call refuses).  Five level launches and one finish on `stream`.
+ * No atomics, fixed summation order in fp64: the same inputs give the same bits on every call, stream and batch size.                        */
+size_t cfen_image_msssim_bytes(int B, int C, int H, int W);
+int cfen_image_msssim(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
+                      void* stream);
+
 /* PNG encoding of uint8 images on the device (csrc/k_png.hip; png.py, test.py --gpu_png): per image one finished zlib stream, the payload of the
  * single IDAT chunk of an 8-bit RGB, non-interlaced PNG.  The caller adds signature, IHDR, the IDAT framing with its CRC-32, and IEND.
  *   stream : 78 01 | per strip: one non-final deflate block, then an empty non-final stored block (000, pad to a byte, 00 00 FF FF) |

@@ -6,7 +6,8 @@
 
 Loads checkpoints/<name>/<which_epoch>_net_G.pth (the reference's own file format), runs the HIP generator on
 every image of <dataroot>/hazy and writes results/<name>/<phase>_<which_epoch>/images/<stem>_fake_A.png.
-With --eval every image is also scored against <dataroot>/clear (PSNR, SSIM) into results/<name>/<phase>_<which_epoch>/metrics.csv.
+With --eval every image is also scored against <dataroot>/clear (PSNR, SSIM) into results/<name>/<phase>_<which_epoch>/metrics.csv;
+--eval_metrics psnr,ssim,msssim adds an MS-SSIM column.
 """
 import logging
 import os
@@ -139,7 +140,8 @@ if __name__ == '__main__':
         # per-image PSNR / SSIM of the written bytes (scored on the device after every test(), models/model_iid_dehazing.py): one metrics.csv in dataset
         # order; under torch.distributed.run the ranks hold consecutive slices, rank 0 gathers their rows over the gloo group and writes the file
         from cfen_vit_dehazing_amd import metrics as _metrics
-        rows = [(os.path.basename(p), a, b) for p, a, b in model.current_metrics()]
+        rows = [(os.path.basename(r[0]),) + tuple(r[1:]) for r in model.current_metrics()]
+        columns = tuple(opt.eval_metrics.split(','))           # --eval_metrics: ('psnr', 'ssim') unless it adds msssim
         if opt.dist_world > 1:
             import torch.distributed as dist
             gathered = [None] * opt.dist_world if opt.dist_rank == 0 else None
@@ -147,8 +149,8 @@ if __name__ == '__main__':
             rows = [r for part in gathered for r in part] if opt.dist_rank == 0 else []
         if opt.dist_rank == 0:
             with open(os.path.join(web_dir, 'metrics.csv'), 'w') as f:
-                f.write(_metrics.format_csv(rows))
-            print(_metrics.summary_line(rows))
+                f.write(_metrics.format_csv(rows) if columns == ('psnr', 'ssim') else _metrics.format_csv_columns(rows, columns))
+            print(_metrics.summary_line(rows) if columns == ('psnr', 'ssim') else _metrics.summary_line_columns(rows, columns))
             print('eval: wrote %s' % os.path.join(web_dir, 'metrics.csv'))
     if opt.dist_world > 1:
         import torch.distributed as dist
