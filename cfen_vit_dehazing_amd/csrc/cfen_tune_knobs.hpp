@@ -166,7 +166,9 @@ CFEN_KNOB(stream_mlp192, "net.stream_mlp192", 1, on_off())
 // latency against 134 -- and gain 2.27 -> 2.24 with several in flight)
 CFEN_KNOB(gvit_stream, "net.gvit_stream", 2, range(0, 2))
 // GViT blocks run their GEMMs as persistent chains (k_gvit.hip): 0 off, 1 (default) every GViT block, 2 the grouped decoder launches only,
-// 3 the encoder blocks only.  Only nets built with fragment-stream GViT weights (cfg.reserved bit 2) can use it.
+// 3 the encoder blocks only, 4 every GEMM of a block as its own one-phase launch of the chain kernel (never split over K: no grid barrier, no
+// split-K seam), 5 as 4 with K split so that a launch has about a workgroup per CU (the in-launch split-K seam, no grid barrier).  Every other
+// value is 0.  Only nets built with fragment-stream GViT weights (cfg.reserved bit 2) can use it.
 CFEN_KNOB(gvit_chain, "net.gvit_chain", 1, any_int())
 // the decoders' output tails (us_conv_d01* ConvTranspose, 3x3, reflect-pad 7x7 + tanh): 0 three launches, 1 ConvTranspose + 3x3 fused
 // (k_up_conv3_fused, round 4) + the 7x7, 2 (default, round 5) the whole tail in one launch (k_tail_fused, both intermediate maps in LDS)

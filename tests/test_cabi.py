@@ -102,6 +102,39 @@ def test_knob_enumeration_is_the_61_keys():
     assert lib.cfen_tune_query(b"gemm.kernel", None, None) == 0            # either pointer may be NULL
 
 
+def test_every_knob_is_swept_or_excused():
+    """the ledger of tests/test_hip_variants.py: every key of the library's table is either swept by that module's GPU tests (SWEPT: key -> the values they
+    run, each accepted by the knob's rule, at least one of them not the shipped default) or excused in EXCLUDED with a reason.  A new knob row fails here until someone
+    tests or excuses it."""
+    from cfen_vit_dehazing_amd import _lib, ops
+    import test_hip_variants as tv
+    lib = _lib.load()
+    keys = ops.tune_keys()
+    assert sorted(keys) == sorted(KNOB_KEYS)
+    missing = [k for k in keys if k not in tv.SWEPT and k not in tv.EXCLUDED]
+    assert not missing, "knobs neither swept by tests/test_hip_variants.py nor excused in its EXCLUDED: %r" % missing
+    assert not set(tv.SWEPT) & set(tv.EXCLUDED) and not (set(tv.SWEPT) | set(tv.EXCLUDED)) - set(keys)
+    assert all(isinstance(r, str) and len(r) > 10 and "\n" not in r for r in tv.EXCLUDED.values())
+    assert "gemm.splitk_stages" in tv.EXCLUDED and "no launcher" in tv.EXCLUDED["gemm.splitk_stages"]
+    for key, values in tv.SWEPT.items():
+        before, shipped = _query(lib, key)
+        assert any(v != shipped for v in values), key
+        for v in values:                        # (validation only: nothing launches)
+            assert lib.cfen_tune(key.encode(), v) == 0, (key, v, lib.cfen_last_error())
+        assert lib.cfen_tune(key.encode(), before) == 0
+    # what the GPU tests iterate is what the ledger shows: every value of SWEPT comes from the operator sweeps or the launch-plan sweeps, and every launch-plan
+    # case (key, value, kind of net) is run by one of the two parametrised tests -- by name, or among the settings that keep the kernel names (NET_DEAD)
+    for key, values in tv.SWEPT.items():
+        assert set(values) == set(tv.OP_SWEPT.get(key, ())) | set(tv.NET_SWEPT.get(key, ())), key
+    assert set(tv.OP_SWEPT) | set(tv.NET_SWEPT) == set(tv.SWEPT)
+    for key, values in tv.NET_SWEPT.items():
+        for v in values:
+            assert [c for c in tv.NET_CASES if c[:2] == (key, v)], "launch-plan setting %s = %d has no case" % (key, v)
+    for case, (needs, reason) in tv.NET_DEAD.items():
+        assert case in tv.NET_CASES, "NET_DEAD names a case that is not swept: %r" % (case,)
+        assert (needs is None or needs.startswith("k_")) and isinstance(reason, str) and len(reason) > 10, case
+
+
 def test_knobs_of_a_fresh_process_are_at_their_shipped_defaults():
     """in an interpreter of its own, so that no test that ran before in this process can matter"""
     import subprocess

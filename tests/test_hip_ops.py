@@ -351,16 +351,37 @@ def test_mlp_block_with_projection_prologue(dtype, D):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("C,H,W,ws", [(24, 64, 32, 32), (48, 32, 48, 16)])
 def test_embed_qkv_fused_front(dtype, C, H, W, ws):
-    """k_embed_qkv (gather + embedding + residual + pos + LN1 + qkv in one launch) against fp64 and the unfused chain"""
+    """k_embed_qkv (gather + embedding + residual + pos + LN1 + qkv in one launch) against fp64 and the unfused chain; the whole body again with
+    k_embed_qkv2's refill right behind the barrier ("embed.defer_refill" 0: data movement only, so bitwise the deferred refill's results)"""
+    _embed_qkv_fused_front(dtype, C, H, W, ws)
+    with ops.tuning({"embed.defer_refill": 0}):
+        _embed_qkv_fused_front(dtype, C, H, W, ws)
+    # the bits, under "embed.lds" 4: as the shipped 6 it selects k_embed_qkv2, the one kernel that reads the knob (fp16; fp32 has no LDS-DMA ring)
     d = dev()
+    fmap, B, p, D, S, we, be, pos, g, b, wq, perm = _embed_front_operands(dtype, C, H, W, ws)
+    args = (fmap, C, ws, p, we[:, perm].contiguous().to(d), be.to(d), pos.to(d), g.to(d), b.to(d), wq[:, perm].contiguous().to(d))
+    with ops.tuning({"embed.lds": 4}):
+        x1, qkv = ops.embed_qkv(*args)
+        with ops.tuning({"embed.defer_refill": 0}):
+            x1n, qkvn = ops.embed_qkv(*args)
+    assert torch.equal(x1, x1n) and torch.equal(qkv, qkvn), "embed.defer_refill 0 differs from 1"
+
+
+def _embed_front_operands(dtype, C, H, W, ws):
     B, p, D = 3, 2, 4 * C
     S = (ws // p) ** 2
-    fmap = ops.to_nhwc(rnd((B, C, H, W), 1, dtype)).to(d)
+    fmap = ops.to_nhwc(rnd((B, C, H, W), 1, dtype)).to(dev())
     we = rnd((D, D), 2, dtype, 1 / math.sqrt(D)); be = rnd((D,), 3, torch.float32, 0.1)
     pos = rnd((S, D), 4, dtype)
     g, b = 1 + rnd((D,), 5, torch.float32, 0.1), rnd((D,), 6, torch.float32, 0.1)
     wq = rnd((3 * D, D), 7, dtype, 1 / math.sqrt(D))
     perm = packing.kperm32(D) if dtype == torch.float16 else torch.arange(D)
+    return fmap, B, p, D, S, we, be, pos, g, b, wq, perm
+
+
+def _embed_qkv_fused_front(dtype, C, H, W, ws):
+    d = dev()
+    fmap, B, p, D, S, we, be, pos, g, b, wq, perm = _embed_front_operands(dtype, C, H, W, ws)
     res = []
     for lds in (0, 3, 4):               # weights straight from L2 / staged through LDS / LDS-DMA ring (fp16 only): same arithmetic
         with ops.tuning({"embed.lds": lds}):
@@ -788,9 +809,11 @@ def test_mlp_stream_block(D, H, M):
     if D == 192:
         # the workgroup shapes of the D = 192 variant (default 22: two 78 KB workgroups a CU on a three-slot ring, 256 registers; 24: four slots; 2 / 3 / 4 token
         # tiles a wave on the six-slot ring of one workgroup a CU) do the same arithmetic per token in the same order
-        for tm in (24, 3, 4, 2):
+        # (25: 22 with the D = 384 kernel's refill placement; 28: one 8-wave workgroup a CU on one shared three-slot ring -- data movement only)
+        for tm in (24, 3, 4, 2, 25, 28):
             with ops.tuning({"mlp3.tm192": tm}):
                 other = ops.mlp_stream_block(x.to(d), sa, b1a.to(d), b2a.to(d), H, ln=(g.to(d), b.to(d)), second=(sb, b1b.to(d), b2b.to(d)), proj=(att.to(d), sp))
+                close(other, full, tol(dtype, 12), "mlp3.tm192 = %d vs fp64" % tm)
                 if tm == 2:     # (the two-tile shape on 512 registers: hipcc contracts one epilogue product differently -- 1 fp16 ulp on a handful of elements)
                     assert float((got.float() - other.float()).abs().max()) <= 2e-3
                 else:
@@ -875,7 +898,10 @@ def test_lvit_window_block_against_oracle_and_unfused_chain(B, H, W):
     got = ops.from_nhwc(ops.lvit_window(fmap, 24, 32, 2, pk, g.name, g.hidden), 24)
     close(got, want, tol(dt, 12), "fused window block vs fp64")
     # the three workgroup shapes (16 waves x 1 token tile: the default; 8 x 2; 4 x 4 on 512 registers) do the same arithmetic per token
-    for shape in (0, 1, 12, 15, 4, 6):       # 12: the refill right behind the barrier; 15: double MLP chunks over the dead K / V tiles (round 6)          # 6: the embedding / K, V matrices in 64-row chunks (5 front chunks instead of 9)          # 4: the attention loops' K / V fragment reads issued by hand ahead of the MFMAs (round 5): same arithmetic, same order
+    with ops.tuning({"lvit.shape": 3}):          # the softmax denominator by MFMA: another summation order, so the fp64 bar and not the bits
+        close(ops.from_nhwc(ops.lvit_window(fmap, 24, 32, 2, pk, g.name, g.hidden), 24), want, tol(dt, 12), "lvit.shape 3 vs fp64")
+    # 5: the 8 x 2 shape with hand-issued K / V fragment reads; 13: 15 with deferred refills
+    for shape in (0, 1, 12, 15, 4, 6, 5, 13):       # 12: the refill right behind the barrier; 15: double MLP chunks over the dead K / V tiles (round 6)          # 6: the embedding / K, V matrices in 64-row chunks (5 front chunks instead of 9)          # 4: the attention loops' K / V fragment reads issued by hand ahead of the MFMAs (round 5): same arithmetic, same order
         with ops.tuning({"lvit.shape": shape}):
             other = ops.from_nhwc(ops.lvit_window(fmap, 24, 32, 2, pk, g.name, g.hidden), 24)
             assert torch.equal(other, got), "lvit.shape %d differs from the default shape" % shape
