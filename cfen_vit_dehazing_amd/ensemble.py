@@ -28,11 +28,12 @@ def actnorm_pending(net):
     return any(int(b) == 0 for k, b in net.named_buffers() if k.endswith("initialized"))
 
 
-def dehaze_x8(net, images, out=None, output_u8=False):
+def dehaze_x8(net, images, out=None, output_u8=False, arena=None):
     """[xr (M,3,T,T), xs (M,1,T,T), xd (M,3,T,T)] float32 of the self-ensemble of `net` (a hipnet.dec_ipt) over `images`: (M,T,T,3) uint8 or
     (M,3,T,T) float32 in [-1,1] CUDA tensor, T = net.cfg.image_size.  With output_u8 three (M,T,T,3) uint8 images instead (util.tensor2im's bytes,
     produced by the merge from the float values).  `out`: optional flat float32 buffer of 7*M*T*T elements that receives [xr | xs | xd] back to back
-    (the layout of net(x, out=)); the results are views of it.
+    (the layout of net(x, out=)); the results are views of it.  `arena`: optional flat contiguous buffer of 56*M*T*T elements (float16 for an
+    output_f16 net, else float32) the eight forwards' outputs go through; its contents before the call do not matter.
 
     A net whose ActNorm layers are uninitialised is refused: they would be initialised from the eight variants of the first image, not from a batch
     of the data as the reference's first call does -- run one plain forward of the first batch first."""
@@ -51,7 +52,11 @@ def dehaze_x8(net, images, out=None, output_u8=False):
     M = images.shape[0]
     odt = torch.float16 if net.output_f16 else torch.float32
     slab = 7 * VARIANTS * T * T
-    arena = torch.empty(M * slab, dtype=odt, device=images.device)
+    if arena is None:
+        arena = torch.empty(M * slab, dtype=odt, device=images.device)
+    elif not isinstance(arena, torch.Tensor) or arena.dim() != 1 or arena.numel() != M * slab or arena.dtype != odt or arena.device != images.device \
+            or not arena.is_contiguous():
+        raise ValueError("dehaze_x8: arena must be a flat contiguous %s buffer of %d elements on the images' device" % (odt, M * slab))
     slab_in = torch.empty((VARIANTS, T, T, 3) if u8 else (VARIANTS, 3, T, T), dtype=images.dtype, device=images.device)
     keep_u8 = net.output_u8
     net.output_u8 = False              # the merge works on the float outputs; bytes come out of the merge

@@ -438,18 +438,18 @@ class dec_ipt(nn.Module):
             return [torch.stack([ops.tensor2im_u8(t[b].contiguous()) for b in range(B)]) for t in (xr, xs, xd)]
         return [xr, xs, xd]
 
-    def forward_tiled(self, image, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=None, self_ensemble=False):
+    def forward_tiled(self, image, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=None, self_ensemble=False, arena=None):
         """[xr, xs, xd] of ONE image of any size, run as overlapping image_size x image_size tiles (tiled.dehaze_tiled); forward() itself keeps
-        refusing anything but the baked-in size.  self_ensemble: every tile runs through forward_x8"""
+        refusing anything but the baked-in size.  self_ensemble: every tile runs through forward_x8; arena: the caller's tile arena (tiled.dehaze_tiled)"""
         from . import tiled
         kw = {} if max_arena_bytes is None else {"max_arena_bytes": max_arena_bytes}
-        return tiled.dehaze_tiled(self, image, overlap=overlap, tile_batch=tile_batch, output_u8=output_u8, self_ensemble=self_ensemble, **kw)
+        return tiled.dehaze_tiled(self, image, overlap=overlap, tile_batch=tile_batch, output_u8=output_u8, self_ensemble=self_ensemble, arena=arena, **kw)
 
-    def forward_x8(self, images, out=None, output_u8=False):
+    def forward_x8(self, images, out=None, output_u8=False, arena=None):
         """[xr, xs, xd] as the mean over the eight flips / transposes of every image (ensemble.dehaze_x8; the reference's Model.forward_x8,
         models/vit_model.py:102-147): one batch-8 forward per image and one merge"""
         from . import ensemble
-        return ensemble.dehaze_x8(self, images, out=out, output_u8=output_u8)
+        return ensemble.dehaze_x8(self, images, out=out, output_u8=output_u8, arena=arena)
 
     def set_scale(self, scale_idx):
         self.scale_idx = scale_idx

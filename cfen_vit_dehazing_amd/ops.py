@@ -20,6 +20,17 @@ def _cuda(*ts):
             raise ValueError("HIP operators need contiguous CUDA tensors")
 
 
+def _out(out, shape, dtype, device, what, zero=False):
+    """the operator's output: `out` if the caller places it (ValueError unless it is a contiguous `dtype` tensor of `shape` on `device`), else a
+    fresh tensor as before (`zero`: the wrappers that have always handed their kernel a zeroed one)"""
+    shape = tuple(int(s) for s in shape)
+    if out is None:
+        return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=device)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shape, device))
+    return out
+
+
 def tune(key, value):
     """process-wide kernel-variant knob (cfen_tune; the table of knobs is csrc/cfen_tune_knobs.hpp); for benchmarks"""
     check(_lib.load().cfen_tune(key.encode(), int(value)), "tune")
@@ -81,24 +92,24 @@ def gemm_nt(x, w, bias=None, residual=None, pos=None, relu=False, out=None):
     return out
 
 
-def gemm_ln(x, wl, s, bias=None, relu=False, eps=1e-5):
+def gemm_ln(x, wl, s, bias=None, relu=False, eps=1e-5, out=None):
     """act(LayerNorm-statistics(x) applied to x @ wl.T: rstd (x wl^T - mean s) + bias); wl / s / bias from packing.ln_folded"""
     _cuda(x, wl, s, bias)
     M, K = x.shape
     N = wl.shape[0]
-    out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    out = _out(out, (M, N), x.dtype, x.device, "gemm_ln")
     check(_lib.load().cfen_gemm_ln(dtype_code(x.dtype), ptr(x), K, ptr(wl), K, ptr(s), ptr(bias), ptr(out), N, M, N, K, int(relu), eps,
                                    current_stream()), "gemm_ln")
     return out
 
 
-def gemm_splitk(x, w, nsplit, bias=None, residual=None, relu=False, lnf_s=None, scratch=None):
+def gemm_splitk(x, w, nsplit, bias=None, residual=None, relu=False, lnf_s=None, scratch=None, out=None):
     """cfen_gemm_splitk: act(x @ w.T + bias) + residual (or the LayerNorm-folded form when lnf_s is given) with K cut into nsplit slices and
     the in-launch reduction; `scratch` (zeroed uint8 buffer) can be passed to check that calls leave its counters zero"""
     _cuda(x, w, bias, residual, lnf_s, scratch)
     M, K = x.shape
     N = w.shape[0]
-    out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    out = _out(out, (M, N), x.dtype, x.device, "gemm_splitk")
     tiles = ((N + 95) // 96) * ((M + 31) // 32)
     if scratch is None:
         scratch = torch.zeros(4096 + tiles * nsplit * 14336, dtype=torch.uint8, device=x.device)
@@ -107,7 +118,7 @@ def gemm_splitk(x, w, nsplit, bias=None, residual=None, relu=False, lnf_s=None, 
     return out
 
 
-def head_conv5(x, w, bias, act=0):
+def head_conv5(x, w, bias, act=0, out=None):
     """cfen_head_conv5: conv5x5 (pad 2) of the network input -- (B,3,H,W) fp32 NCHW or (B,H,W,3) uint8 -- to a (B,H,W,16) fp16 NHWC map;
     w: (Cout <= 16, 3, 5, 5), bias: (Cout,)"""
     from .packing import pack_head5
@@ -118,7 +129,7 @@ def head_conv5(x, w, bias, act=0):
     scale = torch.ones(16, dtype=torch.float32, device=x.device)
     shift = torch.zeros(16, dtype=torch.float32, device=x.device)
     shift[:bias.numel()] = bias.float()
-    out = torch.empty(B, H, W, 16, dtype=torch.float16, device=x.device)
+    out = _out(out, (B, H, W, 16), torch.float16, x.device, "head_conv5")
     check(_lib.load().cfen_head_conv5(1, int(u8), ptr(x), ptr(w5), ptr(scale), ptr(shift), ptr(out), B, H, W, 16, act, current_stream()), "head_conv5")
     return out
 
@@ -158,34 +169,34 @@ def gemm_chain(phases, M, team=48, fold=None, sync=None):
     return int(sync[:8].view(torch.int32)[1].item()) if own else None     # with a caller-owned `sync` buffer: no read-back (word 1 of it = error)
 
 
-def layernorm(x, gamma, beta, eps=1e-5):
+def layernorm(x, gamma, beta, eps=1e-5, out=None):
     _cuda(x, gamma, beta)
-    out = torch.empty_like(x)
+    out = _out(out, x.shape, x.dtype, x.device, "layernorm")
     check(_lib.load().cfen_layernorm(dtype_code(x.dtype), ptr(x), ptr(out), ptr(gamma), ptr(beta), x.shape[0], x.shape[1], eps,
                                      current_stream()), "layernorm")
     return out
 
 
-def attention(qkv, nseq, S, heads):
+def attention(qkv, nseq, S, heads, out=None):
     """qkv: [nseq*S, 3*D] -> [nseq*S, D]"""
     _cuda(qkv)
     D = qkv.shape[1] // 3
-    out = torch.empty(qkv.shape[0], D, dtype=qkv.dtype, device=qkv.device)
+    out = _out(out, (qkv.shape[0], D), qkv.dtype, qkv.device, "attention")
     check(_lib.load().cfen_attention(dtype_code(qkv.dtype), ptr(qkv), ptr(out), nseq, S, heads, D // heads, current_stream()), "attention")
     return out
 
 
-def attention_head_major(qkv, nseq, S, heads):
+def attention_head_major(qkv, nseq, S, heads, out=None):
     """qkv in the head-major layout of embed_qkv(head_major_heads=heads) -> [nseq*S, D] row-major"""
     _cuda(qkv)
     D = qkv.numel() // (3 * nseq * S)
-    out = torch.empty(nseq * S, D, dtype=qkv.dtype, device=qkv.device)
+    out = _out(out, (nseq * S, D), qkv.dtype, qkv.device, "attention_head_major")
     check(_lib.load().cfen_attention_head_major(dtype_code(qkv.dtype), ptr(qkv), ptr(out), nseq, S, heads, D // heads, current_stream()),
           "attention_head_major")
     return out
 
 
-def mlp_block(x, w1a, b1a, w2a, b2a, ln=None, second=None, fold=None, proj=None):
+def mlp_block(x, w1a, b1a, w2a, b2a, ln=None, second=None, fold=None, proj=None, out=None):
     """Fused y1 = x + W2a relu(W1a LN(x)+b1a) + b2a [; y2 = y1 + W2b relu(W1b y1 + b1b) + b2b].
     Weights must already carry packing.kperm32 on their k axis for fp16.  fold = (B, H, W, C, cs, ws, p) writes
     the result into a fresh NHWC map instead of a token matrix.  proj = (att, w_proj): x is first replaced by x + att @ w_proj.T."""
@@ -203,17 +214,17 @@ def mlp_block(x, w1a, b1a, w2a, b2a, ln=None, second=None, fold=None, proj=None)
         _cuda(*second)
         a.w1b, a.b1b, a.w2b, a.b2b = (t.data_ptr() for t in second)
     if fold is None:
-        out = torch.empty_like(x)
+        out = _out(out, x.shape, x.dtype, x.device, "mlp_block")
         a.y = out.data_ptr()
     else:
         B, H, W, C, cs, ws, p = fold
-        out = torch.zeros(B, H, W, cs, dtype=x.dtype, device=x.device)
+        out = _out(out, (B, H, W, cs), x.dtype, x.device, "mlp_block(fold=)", zero=True)
         a.fmap, a.mapH, a.mapW, a.C, a.cs, a.ws, a.p = out.data_ptr(), H, W, C, cs, ws, p
     check(_lib.load().cfen_mlp_block(dtype_code(x.dtype), ctypes.byref(a), current_stream()), "mlp_block")
     return out
 
 
-def mlp_stream_block(x, wa, b1a, b2a, hidden, ln=None, second=None, fold=None, proj=None):
+def mlp_stream_block(x, wa, b1a, b2a, hidden, ln=None, second=None, fold=None, proj=None, out=None):
     """cfen_mlp_stream_block (csrc/k_stream.hip): mlp_block with the matrices as fragment streams.  wa = packing.pack_stream_pair(W1k, W2k);
     second = (wb, b1b, b2b); proj = (att, packing.pack_stream_sq(Wp)); fold = (B, H, W, C, cs, ws, p)."""
     from ._lib import MlpStreamArgsC
@@ -230,23 +241,23 @@ def mlp_stream_block(x, wa, b1a, b2a, hidden, ln=None, second=None, fold=None, p
         _cuda(*second)
         a.wb_stream, a.b1b, a.b2b = (t.data_ptr() for t in second)
     if fold is None:
-        out = torch.empty_like(x)
+        out = _out(out, x.shape, x.dtype, x.device, "mlp_stream_block")
         a.y = out.data_ptr()
     else:
         B, H, W, C, cs, ws, p = fold
-        out = torch.zeros(B, H, W, cs, dtype=x.dtype, device=x.device)
+        out = _out(out, (B, H, W, cs), x.dtype, x.device, "mlp_stream_block(fold=)", zero=True)
         a.fmap, a.mapH, a.mapW, a.C, a.cs, a.ws, a.p = out.data_ptr(), H, W, C, cs, ws, p
     check(_lib.load().cfen_mlp_stream_block(dtype_code(x.dtype), ctypes.byref(a), current_stream()), "mlp_stream_block")
     return out
 
 
-def lvit_window(fmap, C, ws, p, packed, name, hidden, cs_out=None, eps=1e-5):
+def lvit_window(fmap, C, ws, p, packed, name, hidden, cs_out=None, eps=1e-5, out=None):
     """whole LViT block (C = 24, p = 2, ws = 32) map -> map in one launch; `packed` = packing.pack_vit entries of `name` + packing.pack_lvit_window's fragment stream (`hidden` = the stream's hidden width)"""
     from ._lib import LvitArgsC
     _cuda(fmap)
     B, H, W, cs = fmap.shape
     cs_out = cs if cs_out is None else cs_out
-    out = torch.zeros(B, H, W, cs_out, dtype=fmap.dtype, device=fmap.device)
+    out = _out(out, (B, H, W, cs_out), fmap.dtype, fmap.device, "lvit_window", zero=True)
     g = lambda k: packed[name + k].data_ptr()
     a = LvitArgsC(fmap=fmap.data_ptr(), out=out.data_ptr(), B=B, H=H, W=W, C=C, cs_in=cs, cs_out=cs_out, ws=ws, p=p,
                   w_stream=g(".lw.ws"), be=g(".embed.b"), pos=g(".pos"), ln1_gamma=g(".ln1.g"), ln1_beta=g(".ln1.b"),
@@ -256,37 +267,37 @@ def lvit_window(fmap, C, ws, p, packed, name, hidden, cs_out=None, eps=1e-5):
     return out
 
 
-def patchify(fmap, C, ws, p, pool=1):
+def patchify(fmap, C, ws, p, pool=1, out=None):
     """fmap: NHWC [B,Hf,Wf,cs] -> tokens [B*nwin*S, p*p*C] in (i,j,c) feature order."""
     _cuda(fmap)
     B, Hf, Wf, cs = fmap.shape
     H, W = Hf // pool, Wf // pool
-    tok = torch.empty(B * H * W // (p * p), p * p * C, dtype=fmap.dtype, device=fmap.device)
+    tok = _out(out, (B * H * W // (p * p), p * p * C), fmap.dtype, fmap.device, "patchify")
     check(_lib.load().cfen_patchify(dtype_code(fmap.dtype), ptr(fmap), ptr(tok), B, H, W, C, cs, ws, p, pool, current_stream()), "patchify")
     return tok
 
 
-def embed_gather(fmap, C, ws, p, w, bias, pos):
+def embed_gather(fmap, C, ws, p, w, bias, pos, out=None):
     """tokens = patchify(fmap) gathered inside the GEMM:  tok @ w.T + bias + tok + pos[row % len(pos)]  -> [M, p*p*C]"""
     _cuda(fmap, w, bias, pos)
     B, H, W, cs = fmap.shape
     D = p * p * C
-    out = torch.empty(B * H * W // (p * p), D, dtype=fmap.dtype, device=fmap.device)
+    out = _out(out, (B * H * W // (p * p), D), fmap.dtype, fmap.device, "embed_gather")
     check(_lib.load().cfen_embed_gather(dtype_code(fmap.dtype), ptr(fmap), B, H, W, C, cs, ws, p, ptr(w), w.shape[1], ptr(bias), ptr(pos),
                                         pos.shape[0] if pos is not None else 0, ptr(out), D, current_stream()), "embed_gather")
     return out
 
 
-def embed_qkv(fmap, C, ws, p, we, be, pos, ln_g, ln_b, wqkv, eps=1e-5, head_major_heads=0, stream_weights=False):
+def embed_qkv(fmap, C, ws, p, we, be, pos, ln_g, ln_b, wqkv, eps=1e-5, head_major_heads=0, stream_weights=False, out=None):
     """fused LViT front half (D = p*p*C in {96,192}); we / wqkv with the k axis in packing.kperm32 order for fp16.
-    Returns (x1 [M,D], qkv [M,3D])."""
+    Returns (x1 [M,D], qkv [M,3D]); out = (x1, qkv) places them."""
     from ._lib import EmbedQkvArgsC
     _cuda(fmap, we, be, pos, ln_g, ln_b, wqkv)
     B, H, W, cs = fmap.shape
     D = p * p * C
     M = B * H * W // (p * p)
-    x1 = torch.empty(M, D, dtype=fmap.dtype, device=fmap.device)
-    qkv = torch.empty(M, 3 * D, dtype=fmap.dtype, device=fmap.device)
+    x1 = _out(out[0] if out is not None else None, (M, D), fmap.dtype, fmap.device, "embed_qkv (x1)")
+    qkv = _out(out[1] if out is not None else None, (M, 3 * D), fmap.dtype, fmap.device, "embed_qkv (qkv)")
     a = EmbedQkvArgsC(fmap=fmap.data_ptr(), B=B, H=H, W=W, C=C, cs=cs, ws=ws, p=p, we=we.data_ptr(), be=be.data_ptr(), pos=pos.data_ptr(),
                       ln_gamma=ln_g.data_ptr(), ln_beta=ln_b.data_ptr(), wqkv=wqkv.data_ptr(), x1=x1.data_ptr(), qkv=qkv.data_ptr(), eps=eps,
                       head_major_heads=head_major_heads)
@@ -295,32 +306,32 @@ def embed_qkv(fmap, C, ws, p, we, be, pos, ln_g, ln_b, wqkv, eps=1e-5, head_majo
     return x1, qkv
 
 
-def unpatchify(tok, B, H, W, C, cs, ws, p):
+def unpatchify(tok, B, H, W, C, cs, ws, p, out=None):
     _cuda(tok)
-    fmap = torch.zeros(B, H, W, cs, dtype=tok.dtype, device=tok.device)
+    fmap = _out(out, (B, H, W, cs), tok.dtype, tok.device, "unpatchify", zero=True)
     check(_lib.load().cfen_unpatchify(dtype_code(tok.dtype), ptr(tok), ptr(fmap), B, H, W, C, cs, ws, p, current_stream()), "unpatchify")
     return fmap
 
 
-def upsample4(small, cs_out=None):
+def upsample4(small, cs_out=None, out=None):
     _cuda(small)
     B, h, w, cs_in = small.shape
     cs_out = cs_out or cs_in
-    out = torch.zeros(B, 4 * h, 4 * w, cs_out, dtype=small.dtype, device=small.device)
+    out = _out(out, (B, 4 * h, 4 * w, cs_out), small.dtype, small.device, "upsample4", zero=True)
     check(_lib.load().cfen_upsample4(dtype_code(small.dtype), ptr(small), ptr(out), B, h, w, cs_in, cs_in, cs_out, current_stream()), "upsample4")
     return out
 
 
-def nchw_to_nhwc(x, cs, dtype):
+def nchw_to_nhwc(x, cs, dtype, out=None):
     _cuda(x)
     B, C, H, W = x.shape
-    out = torch.empty(B, H, W, cs, dtype=dtype, device=x.device)
+    out = _out(out, (B, H, W, cs), dtype, x.device, "nchw_to_nhwc")
     check(_lib.load().cfen_nchw_to_nhwc(dtype_code(dtype), ptr(x), ptr(out), B, C, H, W, cs, current_stream()), "nchw_to_nhwc")
     return out
 
 
 def conv2d(src0, weight, scale, shift, cin, cout, k=3, stride=1, pad=1, reflect=False, src1=None, transpose=False, act=0,
-           res0=None, res1=None, cs_out=None, nchw_f32=False, rows_layout=False, toeplitz=False, src2=None):
+           res0=None, res1=None, cs_out=None, nchw_f32=False, rows_layout=False, toeplitz=False, src2=None, out=None):
     """src*: NHWC [B,H,W,cs]; weight/scale/shift packed by packing.pack_conv*_weight / affine.
     rows_layout: weight from packing.pack_conv_weight_rows -> the LDS-tiled stride-1 kernel."""
     _cuda(src0, src1, src2, weight, scale, shift, res0, res1)
@@ -331,11 +342,11 @@ def conv2d(src0, weight, scale, shift, cin, cout, k=3, stride=1, pad=1, reflect=
     else:
         Hout, Wout = (Hin + 2 * pad - k) // stride + 1, (Win + 2 * pad - k) // stride + 1
     if nchw_f32:
-        out = torch.empty(B, cout, Hout, Wout, dtype=torch.float32, device=src0.device)
+        out = _out(out, (B, cout, Hout, Wout), torch.float32, src0.device, "conv2d")
         cs_out = cout_pad
     else:
         cs_out = cs_out or round_up(cout, 8)
-        out = torch.zeros(B, Hout, Wout, cs_out, dtype=src0.dtype, device=src0.device)
+        out = _out(out, (B, Hout, Wout, cs_out), src0.dtype, src0.device, "conv2d", zero=True)
     a = ConvArgsC(kind=1 if transpose else 0, k=k, stride=stride, pad=pad, reflect=int(reflect), nsrc=3 if src2 is not None else 2 if src1 is not None else 1,
                   B=B, Hin=Hin, Win=Win, Cin=cin, cs_in=cs_in, Cout=cout, Cout_pad=cout_pad, Kpad=weight.shape[-1], cs_out=cs_out,
                   act=act, out_nchw_f32=int(nchw_f32), cs_res=cs_out, wlayout=2 if toeplitz else int(rows_layout),
@@ -347,37 +358,37 @@ def conv2d(src0, weight, scale, shift, cin, cout, k=3, stride=1, pad=1, reflect=
     return out
 
 
-def _stats_ws(B, device):
+def _stats_ws(B, device, ws=None):
     n = _lib.load().cfen_stats_workspace(B, 128)
-    return torch.empty(n // 4, dtype=torch.float32, device=device)
+    return _out(ws, (n // 4,), torch.float32, device, "stats workspace")
 
 
-def instnorm_relu_(x, C, eps=1e-5):
-    """in place on NHWC [B,H,W,cs]"""
+def instnorm_relu_(x, C, eps=1e-5, stats_ws=None):
+    """in place on NHWC [B,H,W,cs]; stats_ws: the caller's float32 workspace of cfen_stats_workspace(B, 128) bytes (contents irrelevant)"""
     _cuda(x)
     B, H, W, cs = x.shape
-    ws = _stats_ws(B, x.device)
+    ws = _stats_ws(B, x.device, stats_ws)
     check(_lib.load().cfen_instnorm_relu(dtype_code(x.dtype), ptr(x), ptr(ws), B, H * W, C, cs, eps, current_stream()), "instnorm_relu")
     return x
 
 
-def cfsm2g(x0, x1, x2, w, C):
+def cfsm2g(x0, x1, x2, w, C, out=None, stats_ws=None):
     _cuda(x0, x1, x2, w)
     B, H, W, cs = x0.shape
-    out = torch.zeros_like(x0)
-    ws = _stats_ws(B, x0.device)
+    out = _out(out, x0.shape, x0.dtype, x0.device, "cfsm2g", zero=True)
+    ws = _stats_ws(B, x0.device, stats_ws)
     check(_lib.load().cfen_cfsm2g(dtype_code(x0.dtype), ptr(x0), ptr(x1), ptr(x2), ptr(out), ptr(w), ptr(ws), B, H * W, C, cs,
                                   current_stream()), "cfsm2g")
     return out
 
 
-def tensor2im_u8(x):
+def tensor2im_u8(x, out=None):
     """(1|3,H,W) fp32 CUDA tensor in [-1,1] -> (H,W,3) uint8 CUDA tensor; util.tensor2im on the device"""
     _cuda(x)
     if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError("tensor2im_u8 needs a contiguous (C,H,W) float32 tensor")
     C, H, W = x.shape
-    out = torch.empty(H, W, 3, dtype=torch.uint8, device=x.device)
+    out = _out(out, (H, W, 3), torch.uint8, x.device, "tensor2im_u8")
     check(_lib.load().cfen_tensor2im_u8(ptr(x), ptr(out), C, H, W, current_stream()), "tensor2im_u8")
     return out
 
@@ -399,19 +410,23 @@ def tile_gather(img, T, ny, nx, t0, B, out=None):
     return out
 
 
-def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False):
+def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False, out=None):
     """cfen_tile_blend: the tile outputs in `arena` -- the forwards' [xr | xs | xd] output slabs of B tiles each, back to back, float32 or float16 --
-    blended into the H x W image: [xr (3,H,W), xs (1,H,W), xd (3,H,W)] float32, or with output_u8 three (H,W,3) uint8 images (util.tensor2im's bytes)"""
+    blended into the H x W image: [xr (3,H,W), xs (1,H,W), xd (3,H,W)] float32, or with output_u8 three (H,W,3) uint8 images (util.tensor2im's bytes);
+    out = the three tensors, placed by the caller"""
     _cuda(arena)
     need = -(-(ny * nx) // B) * 7 * B * T * T
     if arena.dtype not in (torch.float32, torch.float16) or arena.numel() < need:
         raise ValueError("tile_blend: the arena must hold %d float32 / float16 elements (%d slabs of 7*%d*%d*%d), got %d %s"
                          % (need, need // (7 * B * T * T), B, T, T, arena.numel(), arena.dtype))
     dev = arena.device
+    if out is not None and len(out) != 3:
+        raise ValueError("tile_blend: out must be the three output tensors [xr, xs, xd]")
+    given = out if out is not None else (None, None, None)
     if output_u8:
-        outs = [torch.empty(H, W, 3, dtype=torch.uint8, device=dev) for _ in range(3)]
+        outs = [_out(o, (H, W, 3), torch.uint8, dev, "tile_blend") for o in given]
     else:
-        outs = [torch.empty(c, H, W, dtype=torch.float32, device=dev) for c in (3, 1, 3)]
+        outs = [_out(o, (c, H, W), torch.float32, dev, "tile_blend") for o, c in zip(given, (3, 1, 3))]
     check(_lib.load().cfen_tile_blend(dtype_code(arena.dtype), ptr(arena), B, T, H, W, ny, nx, overlap, int(output_u8), ptr(outs[0]), ptr(outs[1]),
                                       ptr(outs[2]), current_stream()), "tile_blend")
     return outs
@@ -518,10 +533,11 @@ def image_msssim(a, b, value_range=(-1.0, 1.0), out=None):
     return out[:, 0], out[:, 1:].unflatten(1, (5, 2))
 
 
-def png_deflate(images, out=None, out_lengths=None):
+def png_deflate(images, out=None, out_lengths=None, workspace=None):
     """cfen_png_deflate: contiguous (B,H,W,3) uint8 CUDA images -> (slab, lengths): slab (B, out_stride) uint8 holds image b's finished zlib
     stream (the IDAT payload of an 8-bit RGB PNG, png.assemble adds the container) in slab[b, :lengths[b]]; lengths (B,) int32.  The candidate
-    Huffman tables (png.py) are uploaded once per device.  CfenError for an image wider than the encoder's strip (png.geometry)."""
+    Huffman tables (png.py) are uploaded once per device.  workspace: the caller's uint8 scratch of cfen_png_workspace_bytes(B, H, W) bytes (at least
+    16; contents irrelevant), else allocated.  CfenError for an image wider than the encoder's strip (png.geometry)."""
     from . import png
     _cuda(images, out, out_lengths)
     if images.dim() != 4 or images.shape[3] != 3 or images.dtype != torch.uint8 or not images.is_contiguous():
@@ -531,7 +547,7 @@ def png_deflate(images, out=None, out_lengths=None):
     strip, stride = ctypes.c_size_t(0), ctypes.c_size_t(0)
     nbytes = lib.cfen_png_workspace_bytes(B, H, W, ctypes.byref(strip), ctypes.byref(stride))
     tables = png.device_tables(images.device)
-    workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=images.device)
+    workspace = _out(workspace, (max(nbytes, 16),), torch.uint8, images.device, "png_deflate (workspace)")
     if out is None:
         out = torch.empty(B, max(stride.value, 16), dtype=torch.uint8, device=images.device)
     elif nbytes and (tuple(out.shape) != (B, stride.value) or out.dtype != torch.uint8 or not out.is_contiguous()):
@@ -545,13 +561,13 @@ def png_deflate(images, out=None, out_lengths=None):
     return out, out_lengths      # (workspace goes back to torch's allocator on the stream it was used on)
 
 
-def u8hwc_to_nhwc(img, cs, dtype):
+def u8hwc_to_nhwc(img, cs, dtype, out=None):
     """(B,H,W,3) uint8 CUDA tensor -> normalised NHWC [B,H,W,cs] of `dtype` (ToTensor + Normalize(0.5, 0.5) + layout)"""
     _cuda(img)
     if img.dim() != 4 or img.shape[3] != 3 or img.dtype != torch.uint8 or not img.is_contiguous():
         raise ValueError("u8hwc_to_nhwc needs a contiguous (B,H,W,3) uint8 tensor")
     B, H, W, _ = img.shape
-    out = torch.empty(B, H, W, cs, dtype=dtype, device=img.device)
+    out = _out(out, (B, H, W, cs), dtype, img.device, "u8hwc_to_nhwc")
     check(_lib.load().cfen_u8hwc_to_nhwc(dtype_code(dtype), ptr(img), ptr(out), B, H, W, cs, current_stream()), "u8hwc_to_nhwc")
     return out
 

@@ -46,7 +46,7 @@ def tile_grid(H, W, T, overlap):
     return tile_origins(H, T, tile_count(H, T, overlap)), tile_origins(W, T, tile_count(W, T, overlap))
 
 
-def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=MAX_ARENA_BYTES, self_ensemble=False):
+def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=MAX_ARENA_BYTES, self_ensemble=False, arena=None):
     """[xr, xs, xd] of an image of any size through `net` (a hipnet.dec_ipt) as overlapping T x T tiles.
 
     image: (H,W,3) uint8 or (3,H,W) float32 in [-1,1] CUDA tensor; a leading batch dimension of 1 is accepted and kept on the outputs.
@@ -54,7 +54,9 @@ def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_ar
     blend from the float values).  Tiles run tile_batch at a time (the last batch padded with copies of the last tile); a net whose ActNorm layers
     are still uninitialised initialises them from the first tile batch, as its first plain forward would.  An image whose single-tile plan covers
     it (H = W = T) comes out bitwise as the plain forward's.  self_ensemble: every tile batch goes through the geometric self-ensemble
-    (ensemble.dehaze_x8: eight forwards per tile) into a float32 arena, the blend is the same; the ActNorm layers must be initialised then."""
+    (ensemble.dehaze_x8: eight forwards per tile) into a float32 arena, the blend is the same; the ActNorm layers must be initialised then.
+    arena: optional flat contiguous CUDA buffer the tile outputs go through, of exactly ceil(tiles / B) * 7 * B * T * T elements (B = min(tile_batch,
+    tiles)), float16 for an output_f16 net without self_ensemble, else float32; its contents before the call do not matter.  Default: allocated here."""
     if not isinstance(image, torch.Tensor) or not image.is_cuda:
         raise ValueError("dehaze_tiled needs a CUDA tensor image; there is no CPU fallback")
     batched = image.dim() == 4
@@ -82,7 +84,12 @@ def dehaze_tiled(net, image, overlap=None, tile_batch=8, output_u8=False, max_ar
     if arena_bytes > max_arena_bytes:
         raise ValueError("a %d x %d image is %d x %d tiles of %d x %d: their outputs need a %.2f GiB arena, over the %.2f GiB limit (max_arena_bytes)"
                          % (H, W, ny, nx, T, T, arena_bytes / 2 ** 30, max_arena_bytes / 2 ** 30))
-    arena = torch.empty(nslabs * slab, dtype=odt, device=image.device)
+    if arena is None:
+        arena = torch.empty(nslabs * slab, dtype=odt, device=image.device)
+    elif not isinstance(arena, torch.Tensor) or arena.dim() != 1 or arena.numel() != nslabs * slab or arena.dtype != odt or arena.device != image.device \
+            or not arena.is_contiguous():
+        raise ValueError("dehaze_tiled: arena must be a flat contiguous %s buffer of %d elements (%d slabs of 7*%d*%d*%d) on the image's device"
+                         % (odt, nslabs * slab, nslabs, B, T, T))
     slab_in = torch.empty((B, T, T, 3) if u8 else (B, 3, T, T), dtype=image.dtype, device=image.device)
     keep_u8 = net.output_u8
     net.output_u8 = False              # the blend works on the float outputs; bytes come out of the blend, never get blended

@@ -10,6 +10,14 @@
  *   - `dtype` selects storage + MFMA input type: CFEN_F32 (exact fp32 MFMA) or CFEN_F16 (fp16 storage,
  *     fp32 accumulate); biases / norm parameters / affine tables are always fp32;
  *   - feature maps are NHWC with an explicit channel stride `cs`; token matrices are row-major;
+ *   - padding lanes (channels C .. cs - 1 of every pixel) of an OUTPUT map: the convolutions (cfen_conv2d, cfen_head_conv5) and the input layout
+ *     kernels (cfen_nchw_to_nhwc, cfen_u8hwc_to_nhwc) store the whole channel stride, and the lanes past the last channel are exact zeros
+ *     (for the convolutions because packing.py zero-fills the weight rows and the scale / shift entries of the padded output channels, and
+ *     given residuals whose padding is zero).  The kernels that move tokens into a map -- cfen_unpatchify, the fold outputs of cfen_mlp_block /
+ *     cfen_mlp_stream_block / cfen_gemm_chain, cfen_lvit_window -- and cfen_upsample4 store the C channels only and leave the padding lanes
+ *     UNTOUCHED: a caller that needs zeros there zeroes the map once.  cfen_net_forward uses them only on maps with cs == C (24 / 48 / 96
+ *     channels); its maps with padding (12 channels in 16) are all written by convolutions, so the workspace needs no zeroing;
+ *   - scratch and workspace contents are irrelevant before a call unless the function says otherwise (cfen_gemm_splitk's arrival counters);
  *   - all functions are asynchronous on `stream` (a hipStream_t passed as void*), allocate nothing,
  *     return 0 on success or a negative CFEN_ERR_* code; cfen_last_error() gives the message.
  *   - no exceptions cross this boundary.
@@ -257,10 +265,13 @@ typedef struct cfen_lvit_args {
   float eps;
 } cfen_lvit_args;
 int cfen_lvit_window(int dtype, const cfen_lvit_args* a, void* stream);
-/* window partition + unfold (+ optional 4x4 mean pool) / fold + window join          (v3:1025-1056,1140,1186,1274) */
+/* window partition + unfold (+ optional 4x4 mean pool) / fold + window join          (v3:1025-1056,1140,1186,1274)
+ * patchify reads channels 0 .. C - 1 of every pixel (cs >= C) and writes every token element; unpatchify writes channels 0 .. C - 1 of every pixel
+ * and leaves the padding lanes C .. cs - 1 untouched. */
 int cfen_patchify(int dtype, const void* fmap, void* tokens, int B, int H, int W, int C, int cs, int ws, int p, int pool, void* stream);
 int cfen_unpatchify(int dtype, const void* tokens, void* fmap, int B, int H, int W, int C, int cs, int ws, int p, void* stream);
-/* two successive bilinear x2 upsamples, align_corners=False                           (v3:1323) */
+/* two successive bilinear x2 upsamples, align_corners=False; writes channels 0 .. C - 1 of every output pixel, padding lanes C .. cs_out - 1 are left
+ * untouched                                                                             (v3:1323) */
 int cfen_upsample4(int dtype, const void* small, void* out, int B, int h, int w, int C, int cs_in, int cs_out, void* stream);
 int cfen_nchw_to_nhwc(int dtype, const float* in, void* out, int B, int C, int H, int W, int cs, void* stream);
 /* pre / post-processing on the device:
@@ -397,6 +408,7 @@ typedef struct cfen_conv_args {
 } cfen_conv_args;
 int cfen_conv2d(int dtype, const cfen_conv_args* a, void* stream);
 
+/* stats_ws of the two functions below: cfen_stats_workspace(B, C) bytes of fp32 scratch, contents irrelevant before and after the call */
 size_t cfen_stats_workspace(int B, int C);
 /* InstanceNorm2d(affine=False) + ReLU in place                                        (v3:292-302) */
 int cfen_instnorm_relu(int dtype, void* x, float* stats_ws, int B, int HW, int C, int cs, float eps, void* stream);

@@ -1,6 +1,7 @@
 """The C-ABI library loads and exports every symbol include/cfen_hip.h declares (no compute calls: runs
 without a GPU), and the ctypes signature table covers exactly that set."""
 import ctypes
+import inspect
 import os
 import re
 
@@ -133,6 +134,56 @@ def test_every_knob_is_swept_or_excused():
     for case, (needs, reason) in tv.NET_DEAD.items():
         assert case in tv.NET_CASES, "NET_DEAD names a case that is not swept: %r" % (case,)
         assert (needs is None or needs.startswith("k_")) and isinstance(reason, str) and len(reason) > 10, case
+
+
+# functions of the header that launch nothing on the device: queries, set-up and host-side settings
+HOST_ONLY = """cfen_abi_version cfen_last_error cfen_tune cfen_tune_query cfen_tune_key cfen_net_create cfen_net_destroy cfen_net_workspace_bytes
+    cfen_net_set_param cfen_net_actnorm_pending cfen_net_actnorm_pending_count cfen_net_set_input_u8 cfen_net_set_output_u8 cfen_net_set_output_f16
+    cfen_net_missing_params cfen_net_profile_entry cfen_net_profile_entry_kernel cfen_net_stage cfen_net_chain_error_words cfen_net_flops_per_image
+    cfen_image_metrics_bytes cfen_image_msssim_bytes cfen_png_workspace_bytes cfen_stats_workspace cfen_deform_conv_columns_bytes
+    cfen_deform_conv_backward_bytes cfen_deform_conv_backward_set_lds""".split()
+
+
+def test_every_kernel_launching_entry_point_is_guard_band_tested_or_excused():
+    """the ledger of tests/test_hip_bounds.py: every function of include/cfen_hip.h that launches a kernel is run between guard bands by a test of that
+    module (COVERED: entry point -> test) or excused in its NOT_COVERED with a reason.  A new entry point fails here until someone does one or the other."""
+    import test_hip_bounds as tb
+    syms = declared_symbols()
+    assert not set(HOST_ONLY) - set(syms), "HOST_ONLY names functions the header does not declare: %r" % sorted(set(HOST_ONLY) - set(syms))
+    launching = set(syms) - set(HOST_ONLY)
+    missing = sorted(launching - set(tb.COVERED) - set(tb.NOT_COVERED))
+    assert not missing, "entry points neither run by tests/test_hip_bounds.py nor excused in its NOT_COVERED: %r" % missing
+    assert not set(tb.COVERED) & set(tb.NOT_COVERED) and not (set(tb.COVERED) | set(tb.NOT_COVERED)) - launching
+    assert all(isinstance(r, str) and len(r) > 10 and "\n" not in r for r in tb.NOT_COVERED.values())
+    # the test a COVERED entry names is the one that makes the call: by the ops wrapper of that name, or through the C ABI
+    how = {"cfen_embed_qkv_stream": ("stream_weights=True",), "cfen_instnorm_relu": ("ops.instnorm_relu_(",)}
+    for sym, test in tb.COVERED.items():
+        fn = getattr(tb, test, None)
+        assert callable(fn) and test.startswith("test_"), (sym, test)
+        body = inspect.getsource(fn)
+        calls = how.get(sym, ("ops.%s(" % sym[len("cfen_"):], "lib.%s(" % sym))
+        assert any(c in body for c in calls), "%s of tests/test_hip_bounds.py does not call %s" % (test, sym)
+
+
+def test_a_caller_placed_output_is_validated():
+    """ops._out, behind every wrapper's out=: a fresh tensor by default (zeroed where the wrapper always handed its kernel a zeroed one), the caller's tensor
+    if it fits, ValueError naming the operator for a wrong shape, dtype or device, a non-contiguous tensor and something that is no tensor"""
+    import torch
+    from cfen_vit_dehazing_amd import ops
+    cpu = torch.device("cpu")
+    fresh = ops._out(None, (3, 5), torch.float16, cpu, "op")
+    assert fresh.shape == (3, 5) and fresh.dtype == torch.float16 and fresh.device == cpu and fresh.is_contiguous()
+    assert not ops._out(None, (3, 5), torch.float32, cpu, "op", zero=True).any()
+    mine = torch.empty(3, 5, dtype=torch.float16)
+    assert ops._out(mine, (3, 5), torch.float16, cpu, "op") is mine
+    assert ops._out(mine, torch.Size([3, 5]), torch.float16, cpu, "op") is mine
+    bad = {"shape": torch.empty(3, 6, dtype=torch.float16), "rank": torch.empty(15, dtype=torch.float16), "dtype": torch.empty(3, 5, dtype=torch.float32),
+           "device": torch.empty(3, 5, dtype=torch.float16, device="meta"), "strides": torch.empty(5, 3, dtype=torch.float16).t(),
+           "no tensor": [[0.0] * 5] * 3}
+    assert bad["strides"].shape == (3, 5) and not bad["strides"].is_contiguous()
+    for what, t in bad.items():
+        with pytest.raises(ValueError, match="some_op: out must be a contiguous torch.float16 tensor of shape"):
+            ops._out(t, (3, 5), torch.float16, cpu, "some_op")
 
 
 def test_knobs_of_a_fresh_process_are_at_their_shipped_defaults():
