@@ -23,9 +23,7 @@ VARIANTS = 8
 
 def actnorm_pending(net):
     """does `net` (a hipnet.dec_ipt) still hold ActNorm layers that its next eager forward would initialise from its batch?"""
-    if getattr(net, "_packed", None) is not None:
-        return bool(net._an_pending)          # the packed set knows (hipnet._ensure_packed): no walk over the module tree per call
-    return any(int(b) == 0 for k, b in net.named_buffers() if k.endswith("initialized"))
+    return net.actnorm_pending()
 
 
 def dehaze_x8(net, images, out=None, output_u8=False, arena=None):

@@ -5,12 +5,13 @@ Drop-in for the module `define_G(opt, conv)` returns in the reference
   * same 958-key state_dict (strict load of real `<epoch>_net_G.pth` files works, including the
     208.6 M never-used `decoder.*` / `query_embed` parameters, which are kept on the host side only);
   * `net(x)` with x (B,3,H,W) float32 in [-1,1] returns [xr (B,3,H,W), xs (B,1,H,W), xd (B,3,H,W)] float32.
-The arithmetic runs entirely in libcfen_hip.so (csrc/cfen_net.cpp); this class owns parameters,
-packed device copies, the workspace and one C `cfen_net` per batch size.
+The arithmetic runs entirely in libcfen_hip.so (csrc/cfen_net.cpp); this class owns parameters and, per compute type, one
+`_PackedSet`: the packed device copies and the C `cfen_net`s (`_Net`: handle, workspace, graphs) whose pointers refer to them.
 """
 import ctypes
 from ctypes import c_char_p as c_char_p_
 import os
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -53,6 +54,46 @@ def _build_tree(root, manifest):
             mod.register_parameter(parts[-1], nn.Parameter(torch.zeros(shape), requires_grad=False))
 
 
+class _NetKey(NamedTuple):
+    """what one native net is built for (dec_ipt._key)"""
+    batch: int
+    input_u8: bool
+    serial: bool
+    replica: int
+    output_u8: bool
+    dtype: torch.dtype
+    output_f16: bool
+
+
+class _Net:
+    """one native `cfen_net`, its workspace and the graphs captured from it; lives in the `_PackedSet` its parameter pointers refer to"""
+
+    def __init__(self, key, handle, ws, native_u8):
+        self.key, self.handle, self.ws = key, handle, ws      # `ws` is assignable until the first forward (a caller's own buffer of the same size)
+        self.native_u8 = native_u8                             # the net writes uint8 outputs itself
+        self.graphs = {}                                       # capture() id -> (native graph id, the tensors whose addresses the graph bakes in)
+
+
+class _PackedSet:
+    """the packed weights of one compute type on one device and every net built on them.  cfen_net_set_param / cfen_net_actnorm_pending store raw
+    pointers into `packed`, `an_pending` and `ones` without copying: whoever drops this set calls close() first."""
+
+    def __init__(self, dtype, device, packed, an_pending):
+        self.dtype, self.device, self.packed = dtype, device, packed      # packed: {name: device tensor}
+        self.an_pending = an_pending      # packed layer name -> (ActNorm key prefix, conv bias, an_out): uninitialised ActNorm2d layers
+        self.ones = torch.ones(128, dtype=torch.float32, device=device)
+        self.nets = {}                    # _NetKey -> _Net
+
+    def close(self):
+        """destroy every net built on this set; their graphs die with them.  The packed tensors stay usable for new nets."""
+        lib = _lib.load() if self.nets else None
+        for net in self.nets.values():
+            lib.cfen_net_destroy(net.handle)
+            net.handle = net.ws = None
+            net.graphs.clear()
+        self.nets = {}
+
+
 class dec_ipt(nn.Module):
     def __init__(self, opt, conv=None, compute_dtype="fp16"):
         super().__init__()
@@ -63,15 +104,9 @@ class dec_ipt(nn.Module):
         self._manifest = state_manifest(self.cfg)
         _build_tree(self, self._manifest)
         self._dead = {}              # dead key -> CPU tensor, as loaded from a checkpoint (absent = zeros of the manifest shape)
-        self._packed = None          # {name: device tensor} of the current compute dtype
-        self._packed_cache = {}      # other compute dtypes' packed sets (set_compute_dtype)
-        self._packed_dev = None
-        self._an_pending = {}        # packed layer name -> (ActNorm key prefix, conv bias, an_out): uninitialised ActNorm2d layers
-        self._nets = {}              # (batch, input kind, plan, replica, output kind, compute dtype) -> (handle, workspace tensor)
-        self._native_u8 = {}         # same key -> the net writes uint8 outputs itself
-        self._graph_keep = []
-        self._graphs = []            # capture() handle -> (net key, native graph id)
-        self._last = None
+        self._sets = {}              # compute dtype -> _PackedSet (packed weights + the nets built on them); the current one is [self.compute_dtype]
+        self._graphs = []            # capture() id -> the _Net it was captured on (ids are never reused; a closed net has forgotten its graphs)
+        self._last = None            # the _Net of the last forward / capture; None again once that net is closed
         # Launch plan of one forward: two lanes (GViT beside LViT on a second stream / graph branch; best for ONE forward at a time on the default 4
         # hardware queues: 2.75 against 3.44 ms) or one serial chain of launches (what several forwards in flight want -- bench.py, pipeline.py set
         # `serial_plan` themselves -- and what one forward wants once the process runs on more than 4 hardware queues: the two-lane plan's forks / joins
@@ -187,19 +222,20 @@ class dec_ipt(nn.Module):
 
     def invalidate(self):
         """Call after mutating parameters in place; packed copies are rebuilt at the next forward."""
-        self._packed = None
-        self._packed_cache = {}
-        self._free_nets()
+        self._close(self._sets)
+
+    def _close(self, dtypes, forget=True):
+        """close the packed sets of `dtypes` (their nets and graphs die) and, with `forget`, drop their packed weights as well"""
+        for dt in list(dtypes):
+            (self._sets.pop(dt) if forget else self._sets[dt]).close()
+        if self._last is not None and self._last.handle is None:
+            self._last = None
 
     def _free_nets(self):
-        lib = _lib.load() if self._nets else None
-        for h, _ in self._nets.values():
-            lib.cfen_net_destroy(h)
-        self._nets = {}
-        self._native_u8 = {}
-        self._graph_keep = []        # captured graphs died with their nets
-        self._graphs = []
-        self._last = None
+        self._close(self._sets, forget=False)
+
+    def _live_nets(self):
+        return [n for s in self._sets.values() for n in s.nets.values()]
 
     def __del__(self):
         try:
@@ -214,24 +250,18 @@ class dec_ipt(nn.Module):
         if dtype == self.compute_dtype:
             return
         self._check_plan(dtype)
-        if self._packed is not None and not self._an_pending:
+        cur = self._sets.get(self.compute_dtype)
+        if cur is not None and cur.an_pending:
             # (a packed set whose ActNorm layers are still uninitialised is NOT kept: once they are initialised under the other type its epilogue tables and its
-            # pending list would be stale -- the next forward of this type would initialise ActNorm again, from another batch; it is repacked instead.  ADVICE r05)
-            self._packed_cache[self.compute_dtype] = (self._packed, self._packed_dev, self._an_pending, getattr(self, "_ones", None))
+            # pending list would be stale -- the next forward of this type would initialise ActNorm again, from another batch; it is repacked instead, and the
+            # nets already built on it go with it.  ADVICE r05, r06)
+            self._close([self.compute_dtype])
         self.compute_dtype = dtype
-        self._packed = None
-        hit = self._packed_cache.pop(dtype, None)
-        if hit is not None:
-            self._packed, self._packed_dev, self._an_pending, self._ones = hit
 
     def release_other_dtypes(self):
         """free the packed weights, launch plans and workspaces of every compute type but the current one (both types stay resident after a switch: ~0.8 GB of packed
-        weights per type plus each replica's workspace -- what the harness's periodic fp32 checks want, not what a one-off fp32 leg needs afterwards)"""
-        self._packed_cache = {}
-        lib = _lib.load() if self._nets else None
-        for key in [k for k in self._nets if k[5] != self.compute_dtype]:
-            lib.cfen_net_destroy(self._nets.pop(key)[0])
-            self._native_u8.pop(key, None)
+        weights per type plus each replica's workspace -- what the harness's periodic fp32 checks want, not what a one-off fp32 leg needs afterwards).  Graphs captured on the released types die with them: replay() refuses their ids"""
+        self._close([dt for dt in self._sets if dt != self.compute_dtype])
         torch.cuda.empty_cache()
 
     def _live_state(self, device):
@@ -242,28 +272,34 @@ class dec_ipt(nn.Module):
         return sd
 
     def _ensure_packed(self, device):
-        if self._packed is not None and self._packed_dev != device:
+        """the packed set of the current compute type on `device`, packed now if there is none"""
+        pset = self._sets.get(self.compute_dtype)
+        if pset is not None and pset.device != device:
             self.invalidate()
-        if self._packed is None:
+            pset = None
+        if pset is None:
             pending = {}
             packed = pack_state_dict(self._live_state(device), self.cfg, self.compute_dtype, pending=pending, wtile=self.wtile,
                                      gvit_stream=self.gvit_chain)
-            self._packed = {k: v.to(device).contiguous() for k, v in packed.items() if not isinstance(v, str)}
+            tensors = {k: v.to(device).contiguous() for k, v in packed.items() if not isinstance(v, str)}
             for k, v in packed.items():          # "@other": the same device tensor under a second name (shared modules)
                 if isinstance(v, str):
-                    self._packed[k] = self._packed[v[1:]]
-            self._packed_dev = device
+                    tensors[k] = tensors[v[1:]]
             # uninitialised ActNorm2d layers: (key prefix, conv bias [Cout_pad], an_out [2][Cout_pad]) on the device
-            self._an_pending = {n: (an, b.to(device).contiguous(), torch.zeros(2, b.numel(), dtype=torch.float32, device=device))
-                                for n, (an, b) in pending.items()}
-            self._ones = torch.ones(128, dtype=torch.float32, device=device)
-        return self._packed
+            an_pending = {n: (an, b.to(device).contiguous(), torch.zeros(2, b.numel(), dtype=torch.float32, device=device))
+                          for n, (an, b) in pending.items()}
+            pset = self._sets[self.compute_dtype] = _PackedSet(self.compute_dtype, device, tensors, an_pending)
+        return pset
+
+    def _key(self, batch, u8):
+        return _NetKey(batch, bool(u8), bool(self.serial_plan), int(self.replica), bool(self.output_u8), self.compute_dtype, bool(self.output_f16))
 
     def _net_for(self, batch, device, u8=False):
-        packed = self._ensure_packed(device)
-        key = (batch, bool(u8), bool(self.serial_plan), int(self.replica), bool(self.output_u8), self.compute_dtype, bool(self.output_f16))
-        if key in self._nets:
-            return self._nets[key]
+        """the `_Net` for this batch / input kind under the module's current settings, built on the current packed set if it is not there yet"""
+        pset = self._ensure_packed(device)
+        key = self._key(batch, u8)
+        if key in pset.nets:
+            return pset.nets[key]
         if self.gvit_chain:
             # the persistent chains meet at a grid barrier: every team of every forward in flight must be resident at once.  The host caps the team at
             # 256 / (ng x "gvit.max_concurrent") CUs; a replica beyond that number could leave two launches partially resident, spinning on each other
@@ -279,7 +315,7 @@ class dec_ipt(nn.Module):
         # bit 0: single-stream plan; bit 1: tile-major GViT weights; bit 2: GViT fragment streams (persistent chains); bits 8..15: variant
         h = ctypes.c_void_p()
         check(lib.cfen_net_create(ctypes.byref(h), ctypes.byref(cc)), "cfen_net_create")
-        for name, t in packed.items():
+        for name, t in pset.packed.items():
             check(lib.cfen_net_set_param(h, name.encode(), ptr(t), t.numel() * t.element_size()), "cfen_net_set_param(%s)" % name)
         buf = ctypes.create_string_buffer(4096)
         if lib.cfen_net_missing_params(h, buf, 4096):
@@ -292,9 +328,8 @@ class dec_ipt(nn.Module):
                 raise CfenError("output_f16 and output_u8 exclude each other")
             check(lib.cfen_net_set_output_f16(h, 1), "cfen_net_set_output_f16")
         ws = torch.empty(lib.cfen_net_workspace_bytes(h), dtype=torch.uint8, device=device)
-        self._nets[key] = (h, ws)
-        self._native_u8[key] = native_u8
-        return self._nets[key]
+        net = pset.nets[key] = _Net(key, h, ws, native_u8)
+        return net
 
     def plan_info(self):
         """the launch plan the NEXT forward / capture of this module uses, and why (the choice must be visible, not ambient)"""
@@ -309,32 +344,38 @@ class dec_ipt(nn.Module):
         (synchronises; for tests and bench.py's self-check, not for the hot path)"""
         if self._last is None:
             return [0, 0, 0]
-        h, _ = self._nets[self._last]
         words = (ctypes.c_void_p * 3)()
-        check(_lib.load().cfen_net_chain_error_words(h, words, 3), "cfen_net_chain_error_words")
+        check(_lib.load().cfen_net_chain_error_words(self._last.handle, words, 3), "cfen_net_chain_error_words")
         torch.cuda.synchronize()
-        ws = self._nets[self._last][1]          # the words live in the net's workspace tensor: read them through a view of it
+        ws = self._last.ws          # the words live in the net's workspace tensor: read them through a view of it
         return [int(ws[w - ws.data_ptr():w - ws.data_ptr() + 4].view(torch.int32).item()) for w in words]
 
-    def _arm_actnorm_init(self, h):
+    def actnorm_pending(self):
+        """does the module still hold ActNorm layers that its next eager forward would initialise from its batch?"""
+        pset = self._sets.get(self.compute_dtype)
+        if pset is not None:
+            return bool(pset.an_pending)          # the packed set knows (_ensure_packed): no walk over the module tree per call
+        return any(int(b) == 0 for k, b in self.named_buffers() if k.endswith("initialized"))
+
+    def _arm_actnorm_init(self, h, pset):
         """Uninitialised ActNorm2d layers are initialised by the next eager forward, from that batch (models/actnorm.py:25-37)."""
         lib = _lib.load()
-        for name, (an, bias, an_out) in self._an_pending.items():
-            check(lib.cfen_net_actnorm_pending(h, name.encode(), ptr(self._ones), ptr(bias), ptr(an_out)), "cfen_net_actnorm_pending")
+        for name, (an, bias, an_out) in pset.an_pending.items():
+            check(lib.cfen_net_actnorm_pending(h, name.encode(), ptr(pset.ones), ptr(bias), ptr(an_out)), "cfen_net_actnorm_pending")
 
-    def _finish_actnorm_init(self):
+    def _finish_actnorm_init(self, pset):
         """Copy the device-computed ActNorm parameters into the module (so state_dict() / save_networks see what the reference's
         first forward would have left) and flip `initialized`.  The packed epilogue tables were updated in place by the kernel."""
         mods = dict(self.named_modules())
-        for name, (an, bias, an_out) in self._an_pending.items():
+        for name, (an, bias, an_out) in pset.an_pending.items():
             m = mods[an]
             c = m.weight.numel()
             with torch.no_grad():
                 m.weight.copy_(an_out[0, :c])
                 m.bias.copy_(an_out[1, :c])
                 m.initialized.fill_(1)
-        self._packed_cache = {}      # sets of the other compute types were packed before these parameters existed
-        self._an_pending = {}
+        self._close([dt for dt in self._sets if dt != pset.dtype])      # sets of the other compute types were packed before these parameters existed
+        pset.an_pending = {}
 
     # ---- forward ----------------------------------------------------------------------------
     KERNEL_CLASSES = ("gemm", "attention", "layernorm", "tokens", "conv", "norm", "mlp")
@@ -350,14 +391,17 @@ class dec_ipt(nn.Module):
         `x` and the outputs must stay alive and in place while the graph is replayed."""
         res = {}
         outs = self._run(x, out, res, capture=True)
-        self._graph_keep.append((x, outs))
-        self._graphs.append((self._last, res["gid"]))
-        return len(self._graphs) - 1, outs
+        gid = len(self._graphs)
+        self._graphs.append(self._last)
+        self._last.graphs[gid] = (res["gid"], (x, outs))
+        return gid, outs
 
     def replay(self, gid):
-        key, native = self._graphs[gid]
-        h, _ = self._nets[key]
-        check(_lib.load().cfen_net_graph_launch(h, native, current_stream()), "cfen_net_graph_launch")
+        net = self._graphs[gid]
+        if gid not in net.graphs:
+            raise CfenError("graph %d: the net it was captured on has been closed (weights invalidated or its compute type released); "
+                            "capture again" % gid)
+        check(_lib.load().cfen_net_graph_launch(net.handle, net.graphs[gid][0], current_stream()), "cfen_net_graph_launch")
 
     def profile(self, x):
         """One forward with HIP events around every launch: {class: (ms, algorithmic flops, launches)}."""
@@ -380,16 +424,16 @@ class dec_ipt(nn.Module):
             raise ValueError("capture() needs a contiguous float32 / uint8 input (its address is baked into the graph)")
         x = x.contiguous() if u8 else x.contiguous().float()
         B = x.shape[0]
-        h, ws = self._net_for(B, x.device, u8)
-        init_actnorm = bool(self._an_pending)
+        net = self._net_for(B, x.device, u8)
+        h, ws, native_u8 = net.handle, net.ws, net.native_u8
+        pset = self._sets[self.compute_dtype]
+        init_actnorm = bool(pset.an_pending)
         if init_actnorm:
             if capture or prof is not None:
                 raise CfenError("ActNorm2d layers are uninitialised: run one plain forward (it initialises them from its batch, "
                                 "models/actnorm.py:25-37) before capture() / profile()")
-            self._arm_actnorm_init(h)
+            self._arm_actnorm_init(h, pset)
         px = B * n * n
-        key = (B, bool(u8), bool(self.serial_plan), int(self.replica), bool(self.output_u8), self.compute_dtype, bool(self.output_f16))
-        native_u8 = self._native_u8[key]
         if self.output_u8 and out is not None:
             raise ValueError("output_u8 allocates its own (B,H,W,3) uint8 outputs: no `out` slab")
         if capture and self.output_u8 and not native_u8:
@@ -431,8 +475,8 @@ class dec_ipt(nn.Module):
                 i += 1
             prof["launches"] = detail
         if init_actnorm:
-            self._finish_actnorm_init()
-        self._last = key
+            self._finish_actnorm_init(pset)
+        self._last = net
         if self.output_u8 and not native_u8:
             from . import ops
             return [torch.stack([ops.tensor2im_u8(t[b].contiguous()) for b in range(B)]) for t in (xr, xs, xd)]
@@ -459,28 +503,28 @@ class dec_ipt(nn.Module):
         """NCHW float32 copy of a top-level stage output of the last forward (SURVEY Appendix D names)."""
         if self._last is None:
             raise CfenError("no forward has run")
-        h, ws = self._nets[self._last]
+        h, ws, key = self._last.handle, self._last.ws, self._last.key
         p = ctypes.c_void_p()
         C, cs, H, W = (ctypes.c_int32() for _ in range(4))
         check(_lib.load().cfen_net_stage(h, name.encode(), ctypes.byref(p), ctypes.byref(C), ctypes.byref(cs), ctypes.byref(H),
                                          ctypes.byref(W)), "cfen_net_stage")
-        dt = self._last[5]
+        dt = key.dtype
         esz = 2 if dt == torch.float16 else 4
         off = p.value - ws.data_ptr()
-        B = self._last[0]
+        B = key.batch
         n = B * H.value * W.value * cs.value
         flat = ws[off:off + n * esz].view(dt)
         return flat.view(B, H.value, W.value, cs.value)[..., :C.value].permute(0, 3, 1, 2).float().contiguous()
 
     def writes_u8_natively(self):
         """did the net of the last forward write the uint8 images itself (tensor2im in the tails' last launch)?"""
-        return self._last is not None and bool(self._native_u8.get(self._last, False))
+        return self._last is not None and self._last.native_u8
 
     def flops_per_image(self):
-        if not self._nets:
+        nets = self._live_nets()
+        if not nets:
             raise CfenError("no net instantiated yet")
-        h, _ = next(iter(self._nets.values()))
-        return float(_lib.load().cfen_net_flops_per_image(h))
+        return float(_lib.load().cfen_net_flops_per_image(nets[0].handle))
 
 
 def init_weights(net, init_type="kaiming", gain=0.02, seed=None):

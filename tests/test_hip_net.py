@@ -847,7 +847,7 @@ def test_uint8_outputs_written_by_the_tail_equal_tensor2im_of_the_float_outputs(
     want = [o.clone() for o in net(x)]
     net.output_u8 = True
     got = [o.clone() for o in net(x)]
-    assert all(net._native_u8[k] == (dtype == "fp16") for k in net._native_u8 if k[4])
+    assert all(r.native_u8 == (dtype == "fp16") for r in net._live_nets() if r.key.output_u8)
     n = cfg.image_size
     for g, w in zip(got, want):
         assert g.dtype == torch.uint8 and tuple(g.shape) == (batch, n, n, 3)
@@ -1151,3 +1151,66 @@ def test_cli_at_its_default_n_feats_and_hidden_dim_ratio(tmp_path):
         got = np.asarray(Image.open(out_dir / ("syn_%04d_fake_A.png" % (i + 1)))).astype(np.int32)
         assert got.shape == want.shape and np.abs(got - want).max() <= 1
         assert (got != want).mean() < 0.01
+
+
+# ---- nets and graphs live and die with the packed set they point into (hipnet._PackedSet; the host side is tests/test_hip_net_ownership.py) ----
+OWN_CFG = NetConfig(24, 4, patch_size=8, load_size=64)
+
+
+def test_dtype_round_trip_with_pending_actnorm_equals_a_module_that_did_nothing_else():
+    """uninitialised ActNorm, fp16: a refused capture() has already built a net on the packed set; fp32 and back drops that set, so the forward
+    afterwards must run on a net built on the repacked weights -- outputs and the ActNorm parameters it leaves equal a second module's first forward"""
+    from cfen_vit_dehazing_amd._lib import CfenError
+    sd = cached_state_dict(OWN_CFG, mode="reference_init")
+    x = synthetic_input(2, OWN_CFG).to("cuda:0")
+    net, net2 = make_net(OWN_CFG, "fp16", sd=sd), make_net(OWN_CFG, "fp16", sd=sd)
+    with pytest.raises(CfenError):
+        net.capture(x)
+    net.set_compute_dtype("fp32")
+    net.set_compute_dtype("fp16")
+    got, want = net(x), net2(x)
+    torch.cuda.synchronize()
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    sd1, sd2 = net.state_dict(), net2.state_dict()
+    layers = [k[:-len("initialized")] for k in sd1 if k.endswith("initialized")]
+    assert layers
+    for p in layers:
+        assert int(sd1[p + "initialized"]) == 1 and int(sd2[p + "initialized"]) == 1
+        assert torch.equal(sd1[p + "weight"], sd2[p + "weight"]) and torch.equal(sd1[p + "bias"], sd2[p + "bias"])
+
+
+def test_release_other_dtypes_keeps_the_current_types_graphs_and_refuses_the_others():
+    from cfen_vit_dehazing_amd._lib import CfenError
+    net = make_net(OWN_CFG, "fp16")
+    x = synthetic_input(2, OWN_CFG).to("cuda:0")
+    net(x)
+    g16, _ = net.capture(x)
+    net.set_compute_dtype("fp32")
+    eager = [o.clone() for o in net(x)]
+    g32, outs = net.capture(x)
+    assert g32 != g16
+    net.release_other_dtypes()
+    for o in outs:
+        o.fill_(float("nan"))
+    net.replay(g32)
+    torch.cuda.synchronize()
+    for a, b in zip(outs, eager):
+        assert torch.equal(a, b)
+    assert net.capture(x)[0] not in (g16, g32)      # ids already handed out are not reused
+    with pytest.raises(CfenError):
+        net.replay(g16)
+    assert tuple(net.stage("head").shape[:1]) == (2,)
+
+
+def test_release_other_dtypes_forgets_a_last_forward_of_a_released_type():
+    from cfen_vit_dehazing_amd._lib import CfenError
+    net = make_net(OWN_CFG, "fp16")
+    net(synthetic_input(2, OWN_CFG).to("cuda:0"))
+    torch.cuda.synchronize()
+    net.set_compute_dtype("fp32")
+    net.release_other_dtypes()
+    with pytest.raises(CfenError, match="no forward has run"):
+        net.stage("head")
+    assert net.chain_errors() == [0, 0, 0]
+    assert net.writes_u8_natively() is False

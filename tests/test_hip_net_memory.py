@@ -48,13 +48,13 @@ def stage_names(z):
 
 def raw_stage(net, name):
     """the bytes of a stage map of the last forward as they lie in the workspace: every pixel's whole channel stride, padding lanes included"""
-    h, ws = net._nets[net._last]
+    h, ws, key = net._last.handle, net._last.ws, net._last.key
     p = ctypes.c_void_p()
     C, cs, H, W = (ctypes.c_int32() for _ in range(4))
     check(_lib.load().cfen_net_stage(h, name.encode(), ctypes.byref(p), ctypes.byref(C), ctypes.byref(cs), ctypes.byref(H), ctypes.byref(W)), "cfen_net_stage")
-    esz = 2 if net._last[5] == torch.float16 else 4
+    esz = 2 if key.dtype == torch.float16 else 4
     off = p.value - ws.data_ptr()
-    n = net._last[0] * H.value * W.value * cs.value * esz
+    n = key.batch * H.value * W.value * cs.value * esz
     assert 0 <= off and off + n <= ws.numel(), "stage %s lies outside the workspace" % name
     return ws[off:off + n].clone(), C.value, cs.value
 
@@ -62,19 +62,18 @@ def raw_stage(net, name):
 def padding_is_zero(net, name):
     raw, C, cs = raw_stage(net, name)
     if cs > C:
-        lanes = raw.view(net._last[5]).view(-1, cs)[:, C:]
+        lanes = raw.view(net._last.key.dtype).view(-1, cs)[:, C:]
         assert float(lanes.float().abs().max()) == 0.0, "stage %s: padding lanes %d..%d are not exact zeros" % (name, C, cs)
     return cs > C
 
 
 def guard_workspace(net, x, fill):
     """replace the workspace of the net that will run `x` -- before its first forward -- by a guarded buffer of exactly the bytes the library asks for"""
-    h, ws = net._net_for(x.shape[0], x.device, x.dtype == torch.uint8)
-    key = next(k for k, v in net._nets.items() if v[1] is ws)
-    nbytes = _lib.load().cfen_net_workspace_bytes(h)
-    assert nbytes == ws.numel()
+    rec = net._net_for(x.shape[0], x.device, x.dtype == torch.uint8)
+    nbytes = _lib.load().cfen_net_workspace_bytes(rec.handle)
+    assert nbytes == rec.ws.numel()
     g = guarded_empty((nbytes,), torch.uint8, x.device, fill, name="workspace (%s)" % fill, align=256)
-    net._nets[key] = (h, g)
+    rec.ws = g
     return g
 
 
