@@ -13,7 +13,8 @@
 //                   repeat it, so the last batch is full and the batch-B launch plan is reused.  A pure copy.
 //   k_tile_blend  : pull form, PX output pixels per thread; reads the covering tiles straight from the forwards' own output slabs placed one
 //                   after another (the "arena": slab s = tiles [s B, s B + B), each [xr (B,3,T,T) | xs (B,1,T,T) | xd (B,3,T,T)]).  No atomics,
-//                   fixed summation order: run-to-run bitwise.
+//                   fixed summation order: run-to-run bitwise.  lane0 > 0: the image shares its slabs with other images (tiled.pack_plan) and
+//                   its tile t sits at global slot lane0 + t, slab (lane0 + t) / B, lane (lane0 + t) % B.
 #include "cfen_common.hpp"
 
 namespace {
@@ -111,16 +112,16 @@ CFEN_DEV float ld(const half_t* p) { return (float)*p; }
 
 CFEN_DEV unsigned char to_u8(float v) { return (unsigned char)(int)((v + 1.f) / 2.0f * 255.0f); }   // k_tensor2im_u8 (k_tokens.hip)
 
-// the 7 blended planes [xr0 xr1 xr2 xs xd0 xd1 xd2] of output pixel (y, x)
+// the 7 blended planes [xr0 xr1 xr2 xs xd0 xd1 xd2] of output pixel (y, x); the image's tile t sits at global slot lane0 + t of the arena
 template <typename TA>
-CFEN_DEV void blend_pixel(const TA* __restrict__ arena, int B, const TileGeom& g, int o, int y, int x, float (&val)[7]) {
+CFEN_DEV void blend_pixel(const TA* __restrict__ arena, int B, int lane0, const TileGeom& g, int o, int y, int x, float (&val)[7]) {
   const int T = g.T;
   const long long TT = (long long)T * T, slab = 7 * (long long)B * TT;
   int ilo, ihi, jlo, jhi;
   tile_cover(y, g.ny, g.H, T, ilo, ihi);
   tile_cover(x, g.nx, g.W, T, jlo, jhi);
   if (ilo == ihi && jlo == jhi) {          // one tile: its value unchanged (bitwise the plain forward where the image is T x T)
-    const int t = ilo * g.nx + jlo, s = t % B;
+    const int t = lane0 + ilo * g.nx + jlo, s = t % B;
     const TA* base = arena + (long long)(t / B) * slab + (long long)(y - tile_origin(ilo, g.ny, g.H, T)) * T + (x - tile_origin(jlo, g.nx, g.W, T));
 #pragma unroll
     for (int c = 0; c < 3; ++c) val[c] = ld(base + ((long long)s * 3 + c) * TT);
@@ -137,7 +138,7 @@ CFEN_DEV void blend_pixel(const TA* __restrict__ arena, int B, const TileGeom& g
     for (int j = jlo; j <= jhi; ++j) {
       const int v = x - tile_origin(j, g.nx, g.W, T);
       const float w = wy * tile_weight(v, ex, o);
-      const int t = i * g.nx + j, s = t % B;
+      const int t = lane0 + i * g.nx + j, s = t % B;
       const TA* base = arena + (long long)(t / B) * slab + (long long)u * T + v;
 #pragma unroll
       for (int c = 0; c < 3; ++c) acc[c] += w * ld(base + ((long long)s * 3 + c) * TT);
@@ -155,7 +156,7 @@ CFEN_DEV void blend_pixel(const TA* __restrict__ arena, int B, const TileGeom& g
 // plane (outputs 16-byte aligned; element by element at the ragged end of the plane, and everywhere when H W % 4 != 0 leaves the second and
 // third planes of xr / xd unaligned)
 template <typename TA>
-__global__ __launch_bounds__(256) void k_tile_blend_f32(const TA* __restrict__ arena, int B, TileGeom g, int o, float* __restrict__ xr,
+__global__ __launch_bounds__(256) void k_tile_blend_f32(const TA* __restrict__ arena, int B, int lane0, TileGeom g, int o, float* __restrict__ xr,
                                                         float* __restrict__ xs, float* __restrict__ xd) {
   const long long npix = (long long)g.H * g.W, ngroups = (npix + 3) / 4;
   for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < ngroups; q += (long long)gridDim.x * 256) {
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(256) void k_tile_blend_f32(const TA* __restrict__ a
     int y = (int)(p0 / g.W), x = (int)(p0 - (long long)y * g.W);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      if (p0 + e < npix) blend_pixel(arena, B, g, o, y, x, val[e]);
+      if (p0 + e < npix) blend_pixel(arena, B, lane0, g, o, y, x, val[e]);
       if (++x == g.W) { x = 0; ++y; }
     }
     float* planes[7] = {xr, xr + npix, xr + 2 * npix, xs, xd, xd + npix, xd + 2 * npix};
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void k_tile_blend_f32(const TA* __restrict__ a
 // three (H,W,3) uint8 images with util.tensor2im's arithmetic (xs tiled to 3 channels): 16 pixels per thread = 48 bytes per image, three
 // 16-byte stores each (outputs 16-byte aligned; the ragged end byte by byte)
 template <typename TA>
-__global__ __launch_bounds__(256) void k_tile_blend_u8(const TA* __restrict__ arena, int B, TileGeom g, int o, unsigned char* __restrict__ xr,
+__global__ __launch_bounds__(256) void k_tile_blend_u8(const TA* __restrict__ arena, int B, int lane0, TileGeom g, int o, unsigned char* __restrict__ xr,
                                                        unsigned char* __restrict__ xs, unsigned char* __restrict__ xd) {
   const long long npix = (long long)g.H * g.W, ngroups = (npix + 15) / 16;
   for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < ngroups; q += (long long)gridDim.x * 256) {
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void k_tile_blend_u8(const TA* __restrict__ ar
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       float val[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (p0 + e < npix) blend_pixel(arena, B, g, o, y, x, val);
+      if (p0 + e < npix) blend_pixel(arena, B, lane0, g, o, y, x, val);
       if (++x == g.W) { x = 0; ++y; }
       const unsigned char s = to_u8(val[3]);
 #pragma unroll
@@ -262,9 +263,14 @@ int cfen_tile_gather_impl(int u8, const void* src, void* dst, int H, int W, int 
 int cfen_tile_blend_impl(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs,
                          void* xd, hipStream_t s) {
   CFEN_CHECK_ARG(arena && xr && xs && xd, "tile_blend: null pointer");
+  // dtype packs two fields (cfen_hip.h): bits 0..7 the arena element type, bits 8..23 lane0, the lane of the image's tile 0 in its slab
+  CFEN_CHECK_ARG(dtype >= 0 && (dtype >> 24) == 0, "tile_blend: bits 24 and up of dtype = 0x%x must be zero", (unsigned)dtype);
+  const int lane0 = (dtype >> 8) & 0xffff;
+  dtype &= 0xff;
   CFEN_CHECK_ARG(dtype == 0 || dtype == 1, "tile_blend: unknown arena dtype %d", dtype);
   CFEN_CHECK_ARG(out_u8 == 0 || out_u8 == 1, "tile_blend: out_u8 must be 0 or 1");
   CFEN_CHECK_ARG(T >= 2 && T <= 8192 && B >= 1 && B <= 65536, "tile_blend: bad tile edge T = %d or batch B = %d", T, B);
+  CFEN_CHECK_ARG(lane0 < B, "tile_blend: lane0 = %d outside the slab's lanes 0 .. %d", lane0, B - 1);
   CFEN_CHECK_ARG(overlap >= 0 && 2 * overlap <= T, "tile_blend: overlap %d outside 0 .. T/2 = %d", overlap, T / 2);
   CFEN_CHECK_ARG(H >= 1 && W >= 1 && H <= CFEN_TILE_MAX_EDGE && W <= CFEN_TILE_MAX_EDGE, "tile_blend: image size %d x %d outside 1 .. %d", H, W,
                  CFEN_TILE_MAX_EDGE);
@@ -277,17 +283,17 @@ int cfen_tile_blend_impl(int dtype, const void* arena, int B, int T, int H, int 
   if (out_u8) {
     const dim3 grid(tile_grid_for((npix + 15) / 16));
     if (dtype == 1)
-      CFEN_LAUNCH(k_tile_blend_u8<half_t>, grid, dim3(256), 0, s, (const half_t*)arena, B, g, overlap, (unsigned char*)xr, (unsigned char*)xs,
+      CFEN_LAUNCH(k_tile_blend_u8<half_t>, grid, dim3(256), 0, s, (const half_t*)arena, B, lane0, g, overlap, (unsigned char*)xr, (unsigned char*)xs,
                   (unsigned char*)xd);
     else
-      CFEN_LAUNCH(k_tile_blend_u8<float>, grid, dim3(256), 0, s, (const float*)arena, B, g, overlap, (unsigned char*)xr, (unsigned char*)xs,
+      CFEN_LAUNCH(k_tile_blend_u8<float>, grid, dim3(256), 0, s, (const float*)arena, B, lane0, g, overlap, (unsigned char*)xr, (unsigned char*)xs,
                   (unsigned char*)xd);
   } else {
     const dim3 grid(tile_grid_for((npix + 3) / 4));
     if (dtype == 1)
-      CFEN_LAUNCH(k_tile_blend_f32<half_t>, grid, dim3(256), 0, s, (const half_t*)arena, B, g, overlap, (float*)xr, (float*)xs, (float*)xd);
+      CFEN_LAUNCH(k_tile_blend_f32<half_t>, grid, dim3(256), 0, s, (const half_t*)arena, B, lane0, g, overlap, (float*)xr, (float*)xs, (float*)xd);
     else
-      CFEN_LAUNCH(k_tile_blend_f32<float>, grid, dim3(256), 0, s, (const float*)arena, B, g, overlap, (float*)xr, (float*)xs, (float*)xd);
+      CFEN_LAUNCH(k_tile_blend_f32<float>, grid, dim3(256), 0, s, (const float*)arena, B, lane0, g, overlap, (float*)xr, (float*)xs, (float*)xd);
   }
   CFEN_CHECK_LAUNCH("tile_blend");
   return CFEN_OK;

@@ -489,6 +489,13 @@ class dec_ipt(nn.Module):
         kw = {} if max_arena_bytes is None else {"max_arena_bytes": max_arena_bytes}
         return tiled.dehaze_tiled(self, image, overlap=overlap, tile_batch=tile_batch, output_u8=output_u8, self_ensemble=self_ensemble, arena=arena, **kw)
 
+    def forward_tiled_many(self, images, overlap=None, tile_batch=8, output_u8=False, max_arena_bytes=None, self_ensemble=False):
+        """[[xr, xs, xd], ...] of a list of images of any sizes, their tiles packed into common batch-tile_batch forwards (tiled.dehaze_tiled_many);
+        per image what forward_tiled returns.  The ActNorm layers must be initialised."""
+        from . import tiled
+        kw = {} if max_arena_bytes is None else {"max_arena_bytes": max_arena_bytes}
+        return tiled.dehaze_tiled_many(self, images, overlap=overlap, tile_batch=tile_batch, output_u8=output_u8, self_ensemble=self_ensemble, **kw)
+
     def forward_x8(self, images, out=None, output_u8=False, arena=None):
         """[xr, xs, xd] as the mean over the eight flips / transposes of every image (ensemble.dehaze_x8; the reference's Model.forward_x8,
         models/vit_model.py:102-147): one batch-8 forward per image and one merge"""

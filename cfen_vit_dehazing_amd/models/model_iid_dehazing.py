@@ -121,6 +121,35 @@ class DECHLGVIT(BaseModel):
         for path, (p, s) in zip(self.image_paths, metrics.psnr_ssim(out, gt)):
             self._metrics[path] = (p, s)           # an image run again (redone in fp32 after a failed half guard) replaces its row, in place
 
+    # ---- --tile_pack: several images as one group whose tiles share batches (tiled.dehaze_tiled_many) ------------------------------------------------
+    def test_packed(self, inputs):
+        """`inputs`: the loader's batch-1 items of consecutive images, ActNorm layers initialised.  Every image goes through set_input (the pinned
+        staging per shape), the group runs as one packed call, and the per-image state is kept for show_packed(k); returns the number of images."""
+        group = []
+        for item in inputs:
+            self.set_input(item)
+            if self._net_in.shape[0] != 1:
+                raise ValueError('--tile_pack takes batch-1 items (--batchSize 1), got a batch of %d' % self._net_in.shape[0])
+            group.append({'net_in': self._net_in, 'real_B': self.real_B, 'image_paths': self.image_paths, '_gt': self._gt, '_gt_paths': self._gt_paths})
+        self._batch_index += len(group)
+        o = self.opt
+        with torch.no_grad():
+            outs = self.netG.forward_tiled_many([g['net_in'][0] for g in group], overlap=getattr(o, 'tile_overlap', None),
+                                                tile_batch=getattr(o, 'tile_batch', 8), output_u8=getattr(self, '_u8_out', False),
+                                                self_ensemble=getattr(self, '_x8', False))
+        for g, out in zip(group, outs):
+            g['out'] = [t[None] for t in out]              # batch-1 tensors, as forward_tiled hands a batch-1 input back
+        self._packed = group
+        return len(group)
+
+    def show_packed(self, k):
+        """make image k of the last test_packed() the model's current image: what set_input + test leave behind for it (scored under --eval)"""
+        g = self._packed[k]
+        self.real_B, self.image_paths, self._gt, self._gt_paths = g['real_B'], g['image_paths'], g['_gt'], g['_gt_paths']
+        [self.fake_R, self.fake_S, self.fake_A] = g['out']
+        if getattr(self, '_eval', False):
+            self._score()
+
     def current_metrics(self):
         """[(hazy image path, psnr, ssim), ...] of every image scored so far, in the order they first ran; with --eval_metrics psnr,ssim,msssim
         the rows are (hazy image path, psnr, ssim, msssim)"""

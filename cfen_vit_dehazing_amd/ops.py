@@ -410,12 +410,15 @@ def tile_gather(img, T, ny, nx, t0, B, out=None):
     return out
 
 
-def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False, out=None):
+def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False, out=None, lane0=0):
     """cfen_tile_blend: the tile outputs in `arena` -- the forwards' [xr | xs | xd] output slabs of B tiles each, back to back, float32 or float16 --
     blended into the H x W image: [xr (3,H,W), xs (1,H,W), xd (3,H,W)] float32, or with output_u8 three (H,W,3) uint8 images (util.tensor2im's bytes);
-    out = the three tensors, placed by the caller"""
+    out = the three tensors, placed by the caller.  lane0: the lane of the image's tile 0 in the slab `arena` starts at, when the image shares its
+    slabs with other images (tiled.pack_plan): tile t is read from global slot lane0 + t, so the arena holds ceil((lane0 + ny*nx) / B) slabs"""
     _cuda(arena)
-    need = -(-(ny * nx) // B) * 7 * B * T * T
+    if not isinstance(lane0, int) or isinstance(lane0, bool) or not 0 <= lane0 < B:
+        raise ValueError("tile_blend: lane0 = %r must be an int in 0 .. B - 1 = %d" % (lane0, B - 1))
+    need = -(-(lane0 + ny * nx) // B) * 7 * B * T * T
     if arena.dtype not in (torch.float32, torch.float16) or arena.numel() < need:
         raise ValueError("tile_blend: the arena must hold %d float32 / float16 elements (%d slabs of 7*%d*%d*%d), got %d %s"
                          % (need, need // (7 * B * T * T), B, T, T, arena.numel(), arena.dtype))
@@ -427,8 +430,9 @@ def tile_blend(arena, B, T, H, W, ny, nx, overlap, output_u8=False, out=None):
         outs = [_out(o, (H, W, 3), torch.uint8, dev, "tile_blend") for o in given]
     else:
         outs = [_out(o, (c, H, W), torch.float32, dev, "tile_blend") for o, c in zip(given, (3, 1, 3))]
-    check(_lib.load().cfen_tile_blend(dtype_code(arena.dtype), ptr(arena), B, T, H, W, ny, nx, overlap, int(output_u8), ptr(outs[0]), ptr(outs[1]),
-                                      ptr(outs[2]), current_stream()), "tile_blend")
+    # the dtype argument carries two fields (include/cfen_hip.h): bits 0..7 the element type, bits 8..23 lane0
+    check(_lib.load().cfen_tile_blend(dtype_code(arena.dtype) | (lane0 << 8), ptr(arena), B, T, H, W, ny, nx, overlap, int(output_u8), ptr(outs[0]),
+                                      ptr(outs[1]), ptr(outs[2]), current_stream()), "tile_blend")
     return outs
 
 

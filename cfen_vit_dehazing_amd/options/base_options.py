@@ -88,6 +88,10 @@ class BaseOptions():
                             'back to the input size (cfen_vit_dehazing_amd/tiled.py); needs --batchSize 1 and --in_flight 1')
         p.add_argument('--tile_overlap', type=int, default=None, help='(extension) --tile: overlap of neighbouring tiles in pixels (default image_size // 8)')
         p.add_argument('--tile_batch', type=int, default=8, help='(extension) --tile: tiles per forward')
+        p.add_argument('--tile_pack', type=int, default=1,
+                       help='(extension) --tile: run N consecutive images as one group whose tiles share full --tile_batch forwards '
+                            '(tiled.dehaze_tiled_many): a folder of small images runs ceil(tiles / tile_batch) forwards per group instead of at least '
+                            'one short forward per image; same files, names and metrics rows; 1 = one image at a time')
         p.add_argument('--self_ensemble', action='store_true',
                        help='(extension; the reference accepts the flag, base_options.py:133, and never acts on it) geometric self-ensemble: every image '
                             'runs as its eight flips / transposes in one batch-8 forward and the outputs, mapped back, are averaged on the device '
@@ -144,6 +148,13 @@ class BaseOptions():
                                  '(got --batchSize %d --in_flight %d)' % (opt.batchSize, opt.in_flight))
             if opt.tile_batch < 1:
                 raise ValueError('--tile_batch must be >= 1')
+        if getattr(opt, 'tile_pack', 1) < 1:
+            raise ValueError('--tile_pack must be >= 1')
+        if getattr(opt, 'tile_pack', 1) > 1:
+            if not getattr(opt, 'tile', False):
+                raise ValueError('--tile_pack packs the tiles of several images into common batches: it needs --tile')
+            if opt.in_flight != 1:
+                raise ValueError('--tile_pack runs through the sequential loop: it needs --in_flight 1 (got --in_flight %d)' % opt.in_flight)
         if getattr(opt, 'self_ensemble', False) and opt.in_flight != 1:
             raise ValueError('--self_ensemble runs through the sequential loop: it needs --in_flight 1 (got --in_flight %d); the pipelined driver '
                              'replays plain forwards only' % opt.in_flight)
@@ -181,6 +192,8 @@ class BaseOptions():
             args = {k: v for k, v in args.items() if k != 'gpu_png'}                   # ... and so does one without --gpu_png
         if not getattr(opt, 'self_ensemble', False):
             args = {k: v for k, v in args.items() if k != 'self_ensemble'}             # ... and one without --self_ensemble
+        if getattr(opt, 'tile_pack', 1) == 1:
+            args = {k: v for k, v in args.items() if k != 'tile_pack'}                 # ... and one without --tile_pack
         if opt.dist_rank == 0:
             print('------------ Options -------------')
             for k, v in sorted(args.items()):

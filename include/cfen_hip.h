@@ -293,6 +293,10 @@ int cfen_tile_gather(int u8, const void* src, void* dst, int H, int W, int T, in
 /* blend: the tile outputs back into the H x W image.  arena = the forwards' own output slabs back to back, dtype 0 fp32 / 1 fp16 (output_f16 nets):
  *   slab s holds tiles [s B, s B + B) as [xr (B,3,T,T) | xs (B,1,T,T) | xd (B,3,T,T)] (7 B T T elements), tile t in slab t / B, slot t % B;
  *   ceil(ny nx / B) slabs.  ny / nx must be the plan's tile counts for this overlap.
+ * dtype is a bit field: bits 0..7 the arena element type (0 fp32, 1 fp16); bits 8..23 lane0 (default 0), the lane within its slab of the image's
+ *   tile 0 when the image shares its slabs with other images (tiled.pack_plan); bits 24 and up must be zero.  arena then points at the slab that
+ *   holds tile 0, tile t lives at global slot g = lane0 + t (slab g / B, lane g % B), and the image needs ceil((lane0 + ny nx) / B) slabs from
+ *   that pointer.  CFEN_ERR_ARG on an element type other than 0 / 1, on high bits that are set, and on lane0 >= B.  lane0 = 0 is the plain call.
  * Per output pixel: the tile value unchanged where one tile covers it; else sum(w v) / sum(w) in fp32 over the covering tiles in increasing t,
  *   w = w(u) w(v), w(u) = min(1, (min(u, e - 1 - u) + 1) / (o + 1)), e = min(T, L).  No atomics: bitwise reproducible.
  * out_u8 = 0: xr (3,H,W), xs (1,H,W), xd (3,H,W) fp32.  out_u8 = 1: xr / xs / xd each (H,W,3) uint8, tensor2im's arithmetic of the fp32 value

@@ -34,6 +34,32 @@ def _save(opt, image_dir, visuals, paths):
         save_images(image_dir, visuals, paths, aspect_ratio=opt.aspect_ratio, width=opt.display_winsize)
 
 
+def _emit(opt, model, image_dir, i):
+    """the model's current image(s), batch i of the run, to files"""
+    visuals = model.get_current_visuals()
+    if opt.out_all:                       # keep only the dehazed image
+        for item in [k for k in visuals if 'fake_A' not in k]:
+            del visuals[item]
+    img_path = model.get_image_paths()
+    if i % 5 == 0:
+        logging.info('processing (%04d)-th image...' % (i * opt.batchSize))
+    _save(opt, image_dir, visuals, img_path)
+
+
+_PACKED_GROUPS = []          # --tile_pack: images per packed group of this run, for the summary line
+
+
+def _run_packed(opt, model, image_dir, group):
+    """--tile_pack: [(i, data), ...] consecutive batch-1 items as one packed group (models/model_iid_dehazing.py test_packed), then image by image
+    through the same scoring and saving as the loop below"""
+    if group:
+        _PACKED_GROUPS.append(len(group))
+        model.test_packed([data for _, data in group])
+        for k, (i, _) in enumerate(group):
+            model.show_packed(k)
+            _emit(opt, model, image_dir, i)
+
+
 def _rerun_in_fp32(opt, model, image_dir, paths):
     """images whose files came from fp16 forwards later found unsafe (--precision half, a periodic check failed): the model has switched to fp32, run them again"""
     import torch.utils.data
@@ -114,22 +140,29 @@ if __name__ == '__main__':
         _startup["weight_packing_plans_and_warm_up"] = round(time.perf_counter() - _t, 2)
         print('startup seconds %s' % _startup)
         t_loop, n_img = time.perf_counter(), 0
+        pack = getattr(opt, 'tile_pack', 1)
+        group = []
         for i, data in enumerate(dataset):
             if i >= opt.how_many:
                 break
             n_img += len(data['B_paths'])
+            if pack > 1 and not model.netG.actnorm_pending():
+                # --tile_pack: collect N consecutive images, run them as one group (fewer at the end of the data set or at --how_many)
+                group.append((i, data))
+                if len(group) == pack:
+                    _run_packed(opt, model, webpage.get_image_dir(), group)
+                    group = []
+                continue
+            # (with --tile_pack N > 1 only an image that still has to initialise the ActNorm layers comes here: it runs alone, as it always did)
             model.set_input(data)
             model.test(opt)
-            visuals = model.get_current_visuals()
-            if opt.out_all:                       # keep only the dehazed image
-                for item in [k for k in visuals if 'fake_A' not in k]:
-                    del visuals[item]
-            img_path = model.get_image_paths()
-            if i % 5 == 0:
-                logging.info('processing (%04d)-th image...' % (i * opt.batchSize))
-            _save(opt, webpage.get_image_dir(), visuals, img_path)
+            _emit(opt, model, webpage.get_image_dir(), i)
+        _run_packed(opt, model, webpage.get_image_dir(), group)
         t_loop = time.perf_counter() - t_loop
         print('sequential loop: %d images in %.2f s = %.1f images/s file to file' % (n_img, t_loop, n_img / max(t_loop, 1e-9)))
+        if pack > 1:
+            print('--tile_pack %d: %d images in %d packed groups, %d on their own' % (pack, sum(_PACKED_GROUPS), len(_PACKED_GROUPS),
+                                                                                    n_img - sum(_PACKED_GROUPS)))
     model.finish_half_guard()
     if model.redo_paths:
         print('redoing %d images in fp32 (a --precision half check failed after they were written)' % len(model.redo_paths))

@@ -6,6 +6,13 @@ effective bandwidth of the blend kernel against the 6.29 TB/s measured copy rate
 
 The forwards write fp16 outputs straight into the tile arena (output_f16) under fp16; fp32 outputs otherwise.  Device events time each phase of
 the same sequence dehaze_tiled runs; every phase is warmed up first.  Prints one JSON line.
+
+    python tools/bench_tiled.py --pack [--count 16 --height 460 --width 620 --u8]
+
+--pack compares, for --count copies of the image, one dehaze_tiled call per image with one dehaze_tiled_many call over all of them (tiles of
+several images packed into full batches): ms per image of both public calls (device events around each call, the two paths alternating, the
+median of --reps repetitions), the forwards each runs, and the time of its gather and blend launches alone (the same launches on the same
+buffers, median of --reps).
 """
 import argparse
 import json
@@ -24,6 +31,91 @@ from cfen_vit_dehazing_amd.manifest import generate_state_dict
 COPY_TBPS = 6.29          # MI355X_MICROARCH.md: measured device-to-device copy rate
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+def bench_pack(net, args, H, W, T, o, dev):
+    g = torch.Generator().manual_seed(0)
+    if args.u8:
+        imgs = [torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8).to(dev) for _ in range(args.count)]
+    else:
+        imgs = [(torch.rand(3, H, W, generator=g) * 2 - 1).to(dev) for _ in range(args.count)]
+    odt = torch.float16 if net.output_f16 else torch.float32
+    ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
+
+    def timed(fn):
+        a, b = ev(), ev()
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def call_unpacked():
+        for im in imgs:
+            tiled.dehaze_tiled(net, im, overlap=o, tile_batch=args.tile_batch, output_u8=args.u8)
+
+    def call_packed():
+        tiled.dehaze_tiled_many(net, imgs, overlap=o, tile_batch=args.tile_batch, output_u8=args.u8)
+
+    # the gather and blend launches of a path, on buffers of its own: `groups` = the images that share an arena (one each, or all)
+    def phases(groups):
+        state = []
+        for first, last in groups:
+            plan = tiled.pack_plan([(H, W)] * (last - first), T, o, args.tile_batch)
+            slab = 7 * plan.B * T * T
+            arena = torch.zeros(plan.nslabs * slab, dtype=odt, device=dev)
+            slab_in = torch.empty((plan.B, T, T, 3) if args.u8 else (plan.B, 3, T, T), dtype=imgs[0].dtype, device=dev)
+            state.append((first, plan, slab, arena, slab_in))
+
+        def gathers():
+            for first, plan, slab, arena, slab_in in state:
+                for segs in plan.slabs:
+                    for k, t0, count, lane in segs:
+                        ops.tile_gather(imgs[first + k], T, plan.images[k][1], plan.images[k][2], t0, count, out=slab_in[lane:lane + count])
+
+        def blends():
+            for first, plan, slab, arena, slab_in in state:
+                for k, (slot0, ny, nx) in enumerate(plan.images):
+                    ops.tile_blend(arena[(slot0 // plan.B) * slab:], plan.B, T, H, W, ny, nx, o, output_u8=args.u8, lane0=slot0 % plan.B)
+
+        forwards = sum(plan.nslabs for _, plan, _, _, _ in state)
+        slots = sum(plan.nslabs * plan.B for _, plan, _, _, _ in state)
+        launches = sum(len(segs) for _, plan, _, _, _ in state for segs in plan.slabs)
+        return gathers, blends, forwards, slots, launches, state[0][1].B
+
+    paths = {"unpacked": (call_unpacked,) + phases([(k, k + 1) for k in range(args.count)]),
+             "packed": (call_packed,) + phases([(0, args.count)])}
+    times = {name: {"call": [], "gather": [], "blend": []} for name in paths}
+    with torch.no_grad():
+        for name, (call, gathers, blends, *_rest) in paths.items():          # warm-up: plans, workspaces, code objects of every shape in play
+            for _ in range(2):
+                call()
+                gathers()
+                blends()
+        torch.cuda.synchronize()
+        for _ in range(args.reps):                                            # the two paths alternate inside every repetition
+            for name, (call, gathers, blends, *_rest) in paths.items():
+                times[name]["call"].append(timed(call))
+            for name, (call, gathers, blends, *_rest) in paths.items():
+                times[name]["gather"].append(timed(gathers))
+                times[name]["blend"].append(timed(blends))
+    ny, nx = (len(v) for v in tiled.tile_grid(H, W, T, o))
+    res = {"image": [H, W], "count": args.count, "tile": T, "overlap": o, "tiles_per_image": ny * nx, "tile_batch": args.tile_batch,
+           "dtype": args.dtype, "arena": str(odt).replace("torch.", ""), "io": "u8" if args.u8 else "fp32", "reps": args.reps}
+    for name, (call, gathers, blends, forwards, slots, launches, B) in paths.items():
+        t = times[name]
+        res[name] = {"forwards": forwards, "batch": B, "slots": slots, "gather_launches": launches, "blend_launches": args.count,
+                     "ms_per_image": round(_median(t["call"]) / args.count, 4), "ms_total": round(_median(t["call"]), 3),
+                     "ms_total_min_max": [round(min(t["call"]), 3), round(max(t["call"]), 3)],
+                     "ms_gather": round(_median(t["gather"]), 4), "ms_blend": round(_median(t["blend"]), 4),
+                     "ms_gather_blend": round(_median(t["gather"]) + _median(t["blend"]), 4)}
+    res["speedup"] = round(res["unpacked"]["ms_total"] / res["packed"]["ms_total"], 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=2160)
@@ -34,6 +126,8 @@ def main():
     ap.add_argument("--overlap", type=int, default=None)
     ap.add_argument("--u8", action="store_true", help="uint8 image in, uint8 images out (test.py --u8_input); default fp32 in and out")
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--pack", action="store_true", help="compare per-image dehaze_tiled with one packed dehaze_tiled_many over --count images")
+    ap.add_argument("--count", type=int, default=16, help="--pack: number of images in the group")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_tiled.py needs a GPU")
@@ -45,6 +139,9 @@ def main():
     net.output_f16 = args.dtype == "fp16"
     H, W, T = args.height, args.width, cfg.image_size
     o = tiled.default_overlap(T) if args.overlap is None else args.overlap
+    if args.pack:
+        print(json.dumps(bench_pack(net, args, H, W, T, o, dev)))
+        return
     ys, xs = tiled.tile_grid(H, W, T, o)
     ny, nx = len(ys), len(xs)
     n = ny * nx
