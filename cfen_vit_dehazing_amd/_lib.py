@@ -139,6 +139,11 @@ SIGNATURES = {
     "cfen_modulated_deform_conv_backward": (_I, [_I] + [_P] * 11 + [_I] * 16 + [_P, c_size_t, _P]),
 }
 
+# every symbol include/cfen_resample.h declares: an extension with a header of its own; include/cfen_hip.h, SIGNATURES and cfen_abi_version() do not change
+EXTENSION_SIGNATURES = {
+    "cfen_resample_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -151,7 +156,7 @@ def load():
         raise ImportError("libcfen_hip.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "../../include/cfen_hip.h"
+#include "../../include/cfen_resample.h"
 #include "cfen_common.hpp"
 #include "cfen_conv.hpp"
 #include "cfen_internal.hpp"
@@ -313,6 +314,12 @@ int cfen_x8_expand(int u8, const void* src, void* dst, int M, int m, int T, void
 }
 int cfen_x8_merge(int dtype, const void* arena, int M, int T, int out_u8, void* xr, void* xs, void* xd, void* stream) {
   return cfen_x8_merge_impl(dtype, arena, M, T, out_u8, xr, xs, xd, (hipStream_t)stream);
+}
+
+// include/cfen_resample.h
+int cfen_resample_u8(const unsigned char* src, int B, int H, int W, const int* xbounds, const int* xcoef, int xk, int W2, const int* ybounds,
+                     const int* ycoef, int yk, int H2, unsigned char* tmp, unsigned char* dst, void* stream) {
+  return cfen_resample_u8_impl(src, B, H, W, xbounds, xcoef, xk, W2, ybounds, ycoef, yk, H2, tmp, dst, (hipStream_t)stream);
 }
 
 // cfen_tune / cfen_tune_query / cfen_tune_key: cfen_tune.cpp, from the table in cfen_tune_knobs.hpp

@@ -82,6 +82,9 @@ int cfen_png_deflate_impl(const unsigned char* images, int B, int H, int W, cons
 int cfen_tile_gather_impl(int u8, const void* src, void* dst, int H, int W, int T, int ny, int nx, int t0, int B, hipStream_t s);
 int cfen_tile_blend_impl(int dtype, const void* arena, int B, int T, int H, int W, int ny, int nx, int overlap, int out_u8, void* xr, void* xs,
                          void* xd, hipStream_t s);
+// PIL-exact uint8 resampling (k_resample.hip; include/cfen_resample.h)
+int cfen_resample_u8_impl(const unsigned char* src, int B, int H, int W, const int* xbounds, const int* xcoef, int xk, int W2, const int* ybounds,
+                          const int* ycoef, int yk, int H2, unsigned char* tmp, unsigned char* dst, hipStream_t s);
 // geometric self-ensemble (k_ensemble.hip)
 int cfen_x8_expand_impl(int u8, const void* src, void* dst, int M, int m, int T, hipStream_t s);
 int cfen_x8_merge_impl(int dtype, const void* arena, int M, int T, int out_u8, void* xr, void* xs, void* xd, hipStream_t s);

@@ -56,7 +56,8 @@ class _ResizeShortSide:
 def get_transform(opt):
     mode = opt.resize_or_crop
     if mode in ('resize', 'none'):
-        return to_u8_hwc if getattr(opt, 'u8_input', False) else to_normalized_tensor
+        # --fit: the decoded bytes, whether --u8_input is given or not (the device resamples uint8 images, models/model_iid_dehazing.py)
+        return to_u8_hwc if getattr(opt, 'u8_input', False) or getattr(opt, 'fit', False) else to_normalized_tensor
     if mode in ('resize_only', 'scale_width'):
         return _ResizeShortSide(opt.loadSize)
     raise NotImplementedError("--resize_or_crop %s uses random crops (training only)" % mode)

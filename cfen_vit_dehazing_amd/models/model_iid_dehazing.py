@@ -89,6 +89,11 @@ class DECHLGVIT(BaseModel):
         self._eval_msssim = self._eval and 'msssim' in (getattr(opt, 'eval_metrics', None) or '').split(',')      # --eval_metrics psnr,ssim,msssim
         # --self_ensemble: every image (or tile) runs as its eight flips / transposes and the outputs are averaged (ensemble.py); like --tile outside the guard
         self._x8 = bool(getattr(opt, 'self_ensemble', False))
+        # --fit: every image is resampled to the generator's size on the device, runs through the plain branch of forward() -- the fp32 guard included --
+        # and the outputs are resampled back (fit.py); the loader hands over the decoded bytes, --u8_input says which kind of net they go to
+        self._fit = bool(getattr(opt, 'fit', False))
+        self._fit_filter = getattr(opt, 'fit_filter', 'bicubic')
+        self._fit_u8 = bool(getattr(opt, 'u8_input', False))
         if self._tile and self._half_guard:
             print('notice: --precision half with --tile: the fp32 guard does not cover tiled images; they run in fp16 unchecked')
             self._half_guard = False
@@ -300,6 +305,27 @@ class DECHLGVIT(BaseModel):
         return True
 
     def forward(self):
+        if not getattr(self, '_fit', False):
+            return self._forward_native()
+        from .. import fit, ops
+        image = self._net_in                                  # (B,H,W,3) uint8, the decoded file(s); real_B stays the original image
+        T = self.netG.cfg.image_size
+        resized = tuple(image.shape[1:3]) != (T, T)
+        x = ops.resample_u8(image.contiguous(), (T, T), self._fit_filter) if resized else image
+        self._net_in = x if self._fit_u8 else fit.normalize_u8(x)
+        try:
+            self._forward_native()
+        finally:
+            self._net_in = image
+        if resized:
+            outs = []
+            for o in (self.fake_R, self.fake_S, self.fake_A):
+                if o.dtype != torch.uint8:                    # float outputs (the fp32 side of a failed half guard): the bytes that would be written
+                    o = torch.stack([ops.tensor2im_u8(o[b].float().contiguous()) for b in range(o.shape[0])])
+                outs.append(ops.resample_u8(o.contiguous(), image.shape[1:3], self._fit_filter))
+            [self.fake_R, self.fake_S, self.fake_A] = outs
+
+    def _forward_native(self):
         j = self._batch_index
         self._batch_index = j + 1
         x8 = getattr(self, '_x8', False)

@@ -481,6 +481,29 @@ def x8_merge(arena, M, T, output_u8=False, out=None):
     return outs
 
 
+def resample_u8(images_u8, size, filter="bicubic", out=None):
+    """cfen_resample_u8 (include/cfen_resample.h): PIL's Image.resize((W2, H2), filter) of contiguous (B,H,W,3) uint8 CUDA images, byte for byte:
+    (B,H2,W2,3) uint8 for size = (H2, W2).  The integer tables come from resample.coefficients (uploaded once per axis pair, filter and device); the
+    horizontal pass runs if W2 != W into a uint8 intermediate, the vertical pass if H2 != H; with neither the result is a copy.  out: the caller's
+    (B,H2,W2,3) uint8 tensor, which may be a lane of a larger slab (no alignment is assumed)."""
+    from . import resample
+    _cuda(images_u8)
+    if images_u8.dim() != 4 or images_u8.shape[3] != 3 or images_u8.dtype != torch.uint8:
+        raise ValueError("resample_u8 needs a contiguous (B,H,W,3) uint8 tensor, got %s %s" % (tuple(images_u8.shape), images_u8.dtype))
+    B, H, W, _ = images_u8.shape
+    H2, W2 = (int(s) for s in size)
+    if min(B, H, W, H2, W2) < 1:
+        raise ValueError("resample_u8: empty image or target, %s -> %s" % (tuple(images_u8.shape), (H2, W2)))
+    dev = images_u8.device
+    out = _out(out, (B, H2, W2, 3), torch.uint8, dev, "resample_u8")
+    xb, xc = resample.device_tables(W, W2, filter, dev) if W2 != W else (None, None)
+    yb, yc = resample.device_tables(H, H2, filter, dev) if H2 != H else (None, None)
+    tmp = torch.empty(B * H * W2 * 3, dtype=torch.uint8, device=dev) if xb is not None and yb is not None else None
+    check(_lib.load().cfen_resample_u8(ptr(images_u8), B, H, W, ptr(xb), ptr(xc), xc.shape[1] if xc is not None else 0, W2,
+                                       ptr(yb), ptr(yc), yc.shape[1] if yc is not None else 0, H2, ptr(tmp), ptr(out), current_stream()), "resample_u8")
+    return out      # (tmp goes back to torch's allocator on the stream it was used on)
+
+
 def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     """cfen_image_metrics: per image pair (sse, ssim) as two float64 CUDA tensors of shape (B,), in one fused pass.
 

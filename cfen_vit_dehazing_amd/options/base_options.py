@@ -16,6 +16,7 @@ import os
 
 import torch
 
+from .. import resample as _resample
 from ..util import util
 
 
@@ -92,6 +93,13 @@ class BaseOptions():
                        help='(extension) --tile: run N consecutive images as one group whose tiles share full --tile_batch forwards '
                             '(tiled.dehaze_tiled_many): a folder of small images runs ceil(tiles / tile_batch) forwards per group instead of at least '
                             'one short forward per image; same files, names and metrics rows; 1 = one image at a time')
+        p.add_argument('--fit', action='store_true',
+                       help='(extension) dehaze images of any size in ONE forward: every image is resampled to image_size x image_size on the device '
+                            '(PIL\'s Image.resize byte for byte, cfen_vit_dehazing_amd/fit.py; the aspect ratio is not kept), run through the unchanged '
+                            'generator, and the outputs are resampled back to the input size; --batchSize N for equal-sized images; not with --tile, '
+                            'needs --in_flight 1 and --resize_or_crop resize | none')
+        p.add_argument('--fit_filter', type=str, default='bicubic', choices=_resample.FILTERS,
+                       help='(extension) --fit: the resampling filter, both ways (the reference resizes with Image.BICUBIC everywhere)')
         p.add_argument('--self_ensemble', action='store_true',
                        help='(extension; the reference accepts the flag, base_options.py:133, and never acts on it) geometric self-ensemble: every image '
                             'runs as its eight flips / transposes in one batch-8 forward and the outputs, mapped back, are averaged on the device '
@@ -148,6 +156,15 @@ class BaseOptions():
                                  '(got --batchSize %d --in_flight %d)' % (opt.batchSize, opt.in_flight))
             if opt.tile_batch < 1:
                 raise ValueError('--tile_batch must be >= 1')
+        if getattr(opt, 'fit', False):
+            if getattr(opt, 'tile', False):
+                raise ValueError('--fit and --tile are two answers to the same question (one resampled forward, or overlapping tiles): give one of them')
+            if opt.in_flight != 1:
+                raise ValueError('--fit runs through the sequential loop: it needs --in_flight 1 (got --in_flight %d); the pipelined driver '
+                                 'replays plain forwards only' % opt.in_flight)
+            if opt.resize_or_crop not in ('resize', 'none'):
+                raise ValueError('--fit resamples the decoded image itself: it needs --resize_or_crop resize | none (got --resize_or_crop %s, '
+                                 'which resizes in the loader)' % opt.resize_or_crop)
         if getattr(opt, 'tile_pack', 1) < 1:
             raise ValueError('--tile_pack must be >= 1')
         if getattr(opt, 'tile_pack', 1) > 1:
@@ -194,6 +211,8 @@ class BaseOptions():
             args = {k: v for k, v in args.items() if k != 'self_ensemble'}             # ... and one without --self_ensemble
         if getattr(opt, 'tile_pack', 1) == 1:
             args = {k: v for k, v in args.items() if k != 'tile_pack'}                 # ... and one without --tile_pack
+        if not getattr(opt, 'fit', False):
+            args = {k: v for k, v in args.items() if k not in ('fit', 'fit_filter')}   # ... and one without --fit
         if opt.dist_rank == 0:
             print('------------ Options -------------')
             for k, v in sorted(args.items()):
