@@ -144,6 +144,12 @@ EXTENSION_SIGNATURES = {
     "cfen_resample_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
 }
 
+# every symbol include/cfen_guided.h declares: a second extension with a header of its own, bound beside the other two
+GUIDED_SIGNATURES = {
+    "cfen_guided_coef_u8": (_I, [_P, _P, _I, _I, _I, _I, c_float, _P, _P, _P]),
+    "cfen_guided_apply_u8": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
+}
+
 _lib = None
 
 
@@ -156,7 +162,7 @@ def load():
         raise ImportError("libcfen_hip.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

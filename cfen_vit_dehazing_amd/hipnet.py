@@ -502,12 +502,13 @@ class dec_ipt(nn.Module):
         from . import ensemble
         return ensemble.dehaze_x8(self, images, out=out, output_u8=output_u8, arena=arena)
 
-    def forward_fit(self, images, filter="bicubic", self_ensemble=False, u8_input=True):
+    def forward_fit(self, images, filter="bicubic", self_ensemble=False, u8_input=True, refine=None, radius=2, eps=1e-4):
         """[xr, xs, xd], each uint8 at the input's size, of image(s) of ANY size resampled to image_size x image_size, run through one unchanged
         forward and resampled back (fit.dehaze_fit; PIL's Image.resize on the device, the aspect ratio is not kept).  images: (B,H,W,3) uint8, or a
-        list of (H_i,W_i,3) uint8 tensors that run as one batch"""
+        list of (H_i,W_i,3) uint8 tensors that run as one batch.  refine="guided": xd comes back by guided upsampling against the full-resolution
+        input (ops.guided_upsample_u8 with radius and eps) instead of the filter; xr and xs are unchanged by it"""
         from . import fit
-        return fit.dehaze_fit(self, images, filter=filter, self_ensemble=self_ensemble, u8_input=u8_input)
+        return fit.dehaze_fit(self, images, filter=filter, self_ensemble=self_ensemble, u8_input=u8_input, refine=refine, radius=radius, eps=eps)
 
     def set_scale(self, scale_idx):
         self.scale_idx = scale_idx

@@ -94,6 +94,10 @@ class DECHLGVIT(BaseModel):
         self._fit = bool(getattr(opt, 'fit', False))
         self._fit_filter = getattr(opt, 'fit_filter', 'bicubic')
         self._fit_u8 = bool(getattr(opt, 'u8_input', False))
+        # --fit_refine guided: fake_A of a resized image comes back by guided upsampling against the decoded image (fit.back_to_size), not by the filter
+        self._fit_refine = {'none': None}.get(getattr(opt, 'fit_refine', 'none'), getattr(opt, 'fit_refine', 'none'))
+        self._fit_radius = getattr(opt, 'fit_radius', 2)
+        self._fit_eps = getattr(opt, 'fit_eps', 1e-4)
         if self._tile and self._half_guard:
             print('notice: --precision half with --tile: the fp32 guard does not cover tiled images; they run in fp16 unchecked')
             self._half_guard = False
@@ -322,8 +326,9 @@ class DECHLGVIT(BaseModel):
             for o in (self.fake_R, self.fake_S, self.fake_A):
                 if o.dtype != torch.uint8:                    # float outputs (the fp32 side of a failed half guard): the bytes that would be written
                     o = torch.stack([ops.tensor2im_u8(o[b].float().contiguous()) for b in range(o.shape[0])])
-                outs.append(ops.resample_u8(o.contiguous(), image.shape[1:3], self._fit_filter))
-            [self.fake_R, self.fake_S, self.fake_A] = outs
+                outs.append(o.contiguous())
+            [self.fake_R, self.fake_S, self.fake_A] = fit.back_to_size(outs, x, image.contiguous(), self._fit_filter, getattr(self, '_fit_refine', None),
+                                                                       getattr(self, '_fit_radius', 2), getattr(self, '_fit_eps', 1e-4))
 
     def _forward_native(self):
         j = self._batch_index

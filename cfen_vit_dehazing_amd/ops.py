@@ -504,6 +504,70 @@ def resample_u8(images_u8, size, filter="bicubic", out=None):
     return out      # (tmp goes back to torch's allocator on the stream it was used on)
 
 
+def _guided_images(what, **images):
+    for name, t in images.items():
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8 or min(t.shape) < 1:
+            raise ValueError("%s needs %s as a contiguous (B,H,W,3) uint8 tensor, got %s" % (
+                what, name, "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+    _cuda(*images.values())
+
+
+def _guided_params(what, radius, eps):
+    import math
+    try:
+        r, e = int(radius), float(eps)          # Python and numpy scalars, 0-d tensors
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: radius must be an integer in 1 .. 16 and eps a number, got radius %r, eps %r" % (what, radius, eps))
+    if r != radius or not 1 <= r <= 16:
+        raise ValueError("%s: radius must be an integer in 1 .. 16, got %r" % (what, radius))
+    if not (math.isfinite(e) and e > 0):
+        raise ValueError("%s: eps must be finite and > 0, got %r" % (what, eps))
+    return r, e * 255.0 * 255.0          # eps is in squared units of the [0, 1] scale; the kernels work on bytes
+
+
+def guided_coef_u8(guide_lo, src_lo, radius=2, eps=1e-4, out=None):
+    """cfen_guided_coef_u8 (include/cfen_guided.h): the smoothed coefficients of the local linear model src_lo ~ a * guide_lo + b, fitted per pixel
+    and channel over a (2 radius + 1)^2 window: (B,h,w,6) float32 = [abar_R, abar_G, abar_B, bbar_R, bbar_G, bbar_B] on the 0..255 scale.
+    guide_lo, src_lo: contiguous (B,h,w,3) uint8 CUDA tensors; eps regularises the variance, in squared units of the [0, 1] scale.  out: the
+    caller's (B,h,w,6) float32 tensor."""
+    _guided_images("guided_coef_u8", guide_lo=guide_lo, src_lo=src_lo)
+    if guide_lo.shape != src_lo.shape or guide_lo.device != src_lo.device:
+        raise ValueError("guided_coef_u8: guide_lo %s and src_lo %s differ in shape or device" % (tuple(guide_lo.shape), tuple(src_lo.shape)))
+    radius, eps255 = _guided_params("guided_coef_u8", radius, eps)
+    B, h, w, _ = guide_lo.shape
+    dev = guide_lo.device
+    out = _out(out, (B, h, w, 6), torch.float32, dev, "guided_coef_u8")
+    tmp = torch.empty(B, h, w, 6, dtype=torch.float32, device=dev)
+    check(_lib.load().cfen_guided_coef_u8(ptr(guide_lo), ptr(src_lo), B, h, w, radius, eps255, ptr(tmp), ptr(out), current_stream()), "guided_coef_u8")
+    return out      # (tmp goes back to torch's allocator on the stream it was used on)
+
+
+def guided_apply_u8(coef, guide_hi, out=None):
+    """cfen_guided_apply_u8 (include/cfen_guided.h): coef (B,h,w,6) float32 of guided_coef_u8, upsampled bilinearly (half-pixel centres, edge clamp)
+    to the size of guide_hi (B,H,W,3) uint8 and applied to it: (B,H,W,3) uint8 = clamp(floor(Abar * guide_hi + Bbar + 0.5), 0, 255).  out: the
+    caller's (B,H,W,3) uint8 tensor, which may be a lane of a larger slab (no alignment is assumed)."""
+    _guided_images("guided_apply_u8", guide_hi=guide_hi)
+    if not isinstance(coef, torch.Tensor) or coef.dim() != 4 or coef.shape[3] != 6 or coef.dtype != torch.float32 or min(coef.shape) < 1 or \
+            coef.shape[0] != guide_hi.shape[0] or coef.device != guide_hi.device:
+        raise ValueError("guided_apply_u8 needs coef as a contiguous (B,h,w,6) float32 tensor for the %d images of guide_hi, got %s"
+                         % (guide_hi.shape[0], "%s %s" % (tuple(coef.shape), coef.dtype) if isinstance(coef, torch.Tensor) else type(coef).__name__))
+    _cuda(coef)
+    B, H, W, _ = guide_hi.shape
+    out = _out(out, (B, H, W, 3), torch.uint8, guide_hi.device, "guided_apply_u8")
+    check(_lib.load().cfen_guided_apply_u8(ptr(coef), B, coef.shape[1], coef.shape[2], ptr(guide_hi), H, W, ptr(out), current_stream()), "guided_apply_u8")
+    return out
+
+
+def guided_upsample_u8(guide_hi, guide_lo, src_lo, radius=2, eps=1e-4, out=None):
+    """Guided upsampling (He & Sun, "Fast Guided Filter") of src_lo (B,h,w,3) uint8 to the size of guide_hi (B,H,W,3) uint8, where guide_lo
+    (B,h,w,3) is the low-resolution guide src_lo was computed from: guided_apply_u8(guided_coef_u8(guide_lo, src_lo, radius, eps), guide_hi).
+    Three launches."""
+    _guided_images("guided_upsample_u8", guide_hi=guide_hi, guide_lo=guide_lo, src_lo=src_lo)
+    if guide_hi.shape[0] != guide_lo.shape[0]:
+        raise ValueError("guided_upsample_u8: guide_hi %s and guide_lo %s differ in batch" % (tuple(guide_hi.shape), tuple(guide_lo.shape)))
+    return guided_apply_u8(guided_coef_u8(guide_lo, src_lo, radius, eps), guide_hi, out=out)
+
+
 def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     """cfen_image_metrics: per image pair (sse, ssim) as two float64 CUDA tensors of shape (B,), in one fused pass.
 

@@ -100,6 +100,16 @@ class BaseOptions():
                             'needs --in_flight 1 and --resize_or_crop resize | none')
         p.add_argument('--fit_filter', type=str, default='bicubic', choices=_resample.FILTERS,
                        help='(extension) --fit: the resampling filter, both ways (the reference resizes with Image.BICUBIC everywhere)')
+        p.add_argument('--fit_refine', type=str, default='none', choices=('none', 'guided'),
+                       help='(extension) --fit: how the dehazed image comes back to the input size. none: the resampling filter, as for the other '
+                            'outputs. guided: guided upsampling (He & Sun, "Fast Guided Filter") -- a local linear model between the resampled hazy '
+                            'bytes and the dehazed output is fitted at image_size x image_size, smoothed, upsampled and applied to the FULL-resolution '
+                            'hazy image, which supplies the detail (cfen_vit_dehazing_amd/fit.py, include/cfen_guided.h); the other outputs keep the filter')
+        p.add_argument('--fit_radius', type=int, default=2,
+                       help='(extension) --fit_refine guided: radius of the (2 r + 1)^2 window at image_size x image_size, 1 .. 16. The defaults of '
+                            '--fit_radius and --fit_eps come from a synthetic scattering-model experiment (DESIGN section 14), not from a checkpoint')
+        p.add_argument('--fit_eps', type=float, default=1e-4,
+                       help='(extension) --fit_refine guided: regulariser of the local variance, in squared units of the [0, 1] intensity scale, > 0')
         p.add_argument('--self_ensemble', action='store_true',
                        help='(extension; the reference accepts the flag, base_options.py:133, and never acts on it) geometric self-ensemble: every image '
                             'runs as its eight flips / transposes in one batch-8 forward and the outputs, mapped back, are averaged on the device '
@@ -165,6 +175,13 @@ class BaseOptions():
             if opt.resize_or_crop not in ('resize', 'none'):
                 raise ValueError('--fit resamples the decoded image itself: it needs --resize_or_crop resize | none (got --resize_or_crop %s, '
                                  'which resizes in the loader)' % opt.resize_or_crop)
+        if getattr(opt, 'fit_refine', 'none') != 'none' and not getattr(opt, 'fit', False):
+            raise ValueError('--fit_refine chooses how --fit brings the dehazed image back to the input size: it needs --fit')
+        if getattr(opt, 'fit_refine', 'none') != 'none':
+            if not 1 <= opt.fit_radius <= 16:
+                raise ValueError('--fit_refine guided: --fit_radius must be in 1 .. 16 (got --fit_radius %d)' % opt.fit_radius)
+            if not (opt.fit_eps > 0 and opt.fit_eps != float('inf')):
+                raise ValueError('--fit_refine guided: --fit_eps must be finite and > 0 (got --fit_eps %r)' % opt.fit_eps)
         if getattr(opt, 'tile_pack', 1) < 1:
             raise ValueError('--tile_pack must be >= 1')
         if getattr(opt, 'tile_pack', 1) > 1:
@@ -213,6 +230,8 @@ class BaseOptions():
             args = {k: v for k, v in args.items() if k != 'tile_pack'}                 # ... and one without --tile_pack
         if not getattr(opt, 'fit', False):
             args = {k: v for k, v in args.items() if k not in ('fit', 'fit_filter')}   # ... and one without --fit
+        if getattr(opt, 'fit_refine', 'none') == 'none':
+            args = {k: v for k, v in args.items() if k not in ('fit_refine', 'fit_radius', 'fit_eps')}   # ... and one without --fit_refine
         if opt.dist_rank == 0:
             print('------------ Options -------------')
             for k, v in sorted(args.items()):
