@@ -150,6 +150,12 @@ GUIDED_SIGNATURES = {
     "cfen_guided_apply_u8": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
 }
 
+# every symbol include/cfen_colordiff.h declares: the CIEDE2000 extension, bound beside the other three
+COLORDIFF_SIGNATURES = {
+    "cfen_ciede2000_bytes": (c_size_t, [_I, _I, _I]),
+    "cfen_ciede2000_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -162,7 +168,8 @@ def load():
         raise ImportError("libcfen_hip.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()) + \
+            list(COLORDIFF_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -8,6 +8,9 @@ Definition (fixed; include/cfen_hip.h has the long form).  Both images are score
   MS-SSIM  the reference's pytorch_msssim.msssim(window_size=11, size_average=True, val_range=1, normalize=None) (pytorch_msssim/__init__.py:73-107):
         five levels of 2 x 2 means, at each the mean SSIM and the mean cs = (2 sigma12 + C2) / (sigma1^2 + sigma2^2 + C2) from the device
         (ops.image_msssim), then prod_{l<4} cs_l^w_l * ssim_4^w_4 here in float64; NaN when one of those five terms is negative, as in the reference.
+  CIEDE2000  the mean over the pixels of the colour difference dE00 (Sharma, Wu and Dalal 2005, kL = kC = kH = 1) between the two images read as
+        8-bit sRGB: bytes -> linear light by a 256-entry table -> XYZ at the matrix's own white -> Lab, a pixel with R = G = B achromatic by
+        definition (include/cfen_colordiff.h has the long form).  uint8 images only; its own flag --eval_ciede2000, not a name of --eval_metrics.
 Images under 11 x 11 (MS-SSIM: under 176 x 176) are refused: the reference shrinks its window there, this project does not follow it.
 
 CUDA tensors only; there is no CPU fallback.  `format_csv` / `summarize` are the text side of test.py --eval."""
@@ -16,6 +19,7 @@ import math
 CSV_HEADER = "image,psnr,ssim"
 COLUMNS = ("psnr", "ssim", "msssim")                                 # what --eval_metrics may name, in the order of the csv
 MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+CIEDE_COLUMN = "ciede2000"                                           # --eval_ciede2000: the csv's last column, after what --eval_metrics selected
 MSSSIM_MIN_EDGE = 176                                                # 11 * 2^4: the fifth level still holds one window
 
 
@@ -70,12 +74,31 @@ def psnr_ssim_msssim(out, gt, value_range=(-1.0, 1.0)):
     return [(psnr_from_sse(r[0], n), float(r[1]), msssim_from_levels([r[1 + 2 * l:3 + 2 * l] for l in range(5)])) for r in host]
 
 
+def srgb_linear_table():
+    """the 256 float32 values lin[v] of include/cfen_colordiff.h: with c = v / 255, c / 12.92 if c <= 0.04045, otherwise ((c + 0.055) / 1.055)^2.4,
+    evaluated in float64 and rounded once; a numpy array (ops.image_ciede2000 uploads it once per device)"""
+    import numpy as np
+    c = np.arange(256, dtype=np.float64) / 255.0
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(np.float32)
+
+
+def ciede2000(out, gt):
+    """[mean dE00, ...] per image, Python floats.  out, gt: (B,H,W,3) / (H,W,3) uint8 CUDA tensors of equal shape, read as sRGB; out is colour 1.
+    One device call (two launches) and one copy of 8 B bytes back."""
+    import torch
+    from . import ops
+    if not isinstance(out, torch.Tensor) or not isinstance(gt, torch.Tensor) or not out.is_cuda or not gt.is_cuda:
+        raise ValueError("ciede2000 needs CUDA tensors; there is no CPU fallback")
+    return [float(v) for v in ops.image_ciede2000(out.contiguous(), gt.contiguous()).cpu().tolist()]
+
+
 def parse_columns(text):
     """--eval_metrics: 'psnr,ssim' or 'psnr,ssim,msssim' -> the tuple of columns; psnr and ssim are always written, in the csv's fixed order"""
     names = [t.strip() for t in str(text).split(",") if t.strip()]
     for n in names:
         if n not in COLUMNS:
-            raise ValueError("--eval_metrics: unknown metric '%s' (known: %s)" % (n, ", ".join(COLUMNS)))
+            raise ValueError("--eval_metrics: unknown metric '%s' (known: %s)%s" % (
+                n, ", ".join(COLUMNS), "; CIEDE2000 has a flag of its own, --eval_ciede2000" if n == CIEDE_COLUMN else ""))
     if len(set(names)) != len(names) or "psnr" not in names or "ssim" not in names:
         raise ValueError("--eval_metrics: psnr and ssim are always written, each name once: psnr,ssim or psnr,ssim,msssim (got '%s')" % text)
     return tuple(c for c in COLUMNS if c in names)
@@ -121,7 +144,7 @@ def format_csv_columns(rows, columns):
 
 def summarize_columns(rows, columns):
     """summarize() of the psnr and ssim columns, plus with 'msssim': 'msssim_mean' (over the rows that are not NaN, nan when there is none) and
-    'msssim_nan' (how many are NaN)"""
+    'msssim_nan' (how many are NaN), and with 'ciede2000': 'ciede2000_mean' (nan without rows)"""
     ip, iss = 1 + list(columns).index("psnr"), 1 + list(columns).index("ssim")
     s = summarize([(r[0], r[ip], r[iss]) for r in rows])
     if "msssim" in columns:
@@ -129,6 +152,9 @@ def summarize_columns(rows, columns):
         good = [r[im] for r in rows if not math.isnan(r[im])]
         s["msssim_mean"] = sum(good) / len(good) if good else float("nan")
         s["msssim_nan"] = len(rows) - len(good)
+    if CIEDE_COLUMN in columns:
+        ic = 1 + list(columns).index(CIEDE_COLUMN)
+        s["ciede2000_mean"] = sum(r[ic] for r in rows) / len(rows) if rows else float("nan")
     return s
 
 
@@ -138,4 +164,6 @@ def summary_line_columns(rows, columns):
     if "msssim" in columns:
         s = summarize_columns(rows, columns)
         line += ", mean MS-SSIM %.6f over %d (%d nan)" % (s["msssim_mean"], s["images"] - s["msssim_nan"], s["msssim_nan"])
+    if CIEDE_COLUMN in columns:
+        line += ", mean CIEDE2000 %.4f" % summarize_columns(rows, columns)["ciede2000_mean"]
     return line

@@ -87,6 +87,7 @@ class DECHLGVIT(BaseModel):
         self._eval = bool(getattr(opt, 'eval', False))
         self._metrics = {}
         self._eval_msssim = self._eval and 'msssim' in (getattr(opt, 'eval_metrics', None) or '').split(',')      # --eval_metrics psnr,ssim,msssim
+        self._eval_ciede = self._eval and bool(getattr(opt, 'eval_ciede2000', False))      # --eval_ciede2000: one more column, one more device call
         # --self_ensemble: every image (or tile) runs as its eight flips / transposes and the outputs are averaged (ensemble.py); like --tile outside the guard
         self._x8 = bool(getattr(opt, 'self_ensemble', False))
         # --fit: every image is resampled to the generator's size on the device, runs through the plain branch of forward() -- the fp32 guard included --
@@ -123,12 +124,14 @@ class DECHLGVIT(BaseModel):
         if tuple(out.shape) != tuple(gt.shape):
             raise ValueError('--eval: the ground truth %s is %d x %d but the output for %s is %d x %d'
                              % (self._gt_paths[0], gt.shape[1], gt.shape[2], self.image_paths[0], out.shape[1], out.shape[2]))
+        # --eval_ciede2000: the mean colour difference of the same bytes, appended to whatever row --eval_metrics selected
+        extra = [(d,) for d in metrics.ciede2000(out, gt)] if getattr(self, '_eval_ciede', False) else [()] * out.shape[0]
         if getattr(self, '_eval_msssim', False):
-            for path, row in zip(self.image_paths, metrics.psnr_ssim_msssim(out, gt)):
-                self._metrics[path] = row          # (psnr, ssim, msssim): the one device call serves the whole row
+            for path, row, e in zip(self.image_paths, metrics.psnr_ssim_msssim(out, gt), extra):
+                self._metrics[path] = tuple(row) + e          # (psnr, ssim, msssim): the one device call serves the whole row
             return
-        for path, (p, s) in zip(self.image_paths, metrics.psnr_ssim(out, gt)):
-            self._metrics[path] = (p, s)           # an image run again (redone in fp32 after a failed half guard) replaces its row, in place
+        for path, (p, s), e in zip(self.image_paths, metrics.psnr_ssim(out, gt), extra):
+            self._metrics[path] = (p, s) + e       # an image run again (redone in fp32 after a failed half guard) replaces its row, in place
 
     # ---- --tile_pack: several images as one group whose tiles share batches (tiled.dehaze_tiled_many) ------------------------------------------------
     def test_packed(self, inputs):
@@ -161,7 +164,7 @@ class DECHLGVIT(BaseModel):
 
     def current_metrics(self):
         """[(hazy image path, psnr, ssim), ...] of every image scored so far, in the order they first ran; with --eval_metrics psnr,ssim,msssim
-        the rows are (hazy image path, psnr, ssim, msssim)"""
+        the rows are (hazy image path, psnr, ssim, msssim); --eval_ciede2000 appends the mean CIEDE2000 to either"""
         return [(path,) + tuple(row) for path, row in getattr(self, '_metrics', {}).items()]
 
     def _guard_dir(self):

@@ -624,6 +624,45 @@ def image_msssim(a, b, value_range=(-1.0, 1.0), out=None):
     return out[:, 0], out[:, 1:].unflatten(1, (5, 2))
 
 
+_srgb_tables = {}      # device -> the 256-entry sRGB-to-linear table of include/cfen_colordiff.h
+
+
+def _srgb_table(device):
+    if device not in _srgb_tables:
+        from . import metrics
+        _srgb_tables[device] = torch.from_numpy(metrics.srgb_linear_table()).to(device)
+    return _srgb_tables[device]
+
+
+def image_ciede2000(a, b, map=None, out=None):
+    """cfen_ciede2000_u8 (include/cfen_colordiff.h): per image pair the mean CIEDE2000 colour difference as a float64 CUDA tensor of shape (B,).
+
+    a, b: (B,H,W,3) uint8 CUDA tensors read as sRGB (a is colour 1); an image without the batch dimension is taken as a batch of one.  map: None,
+    True (a fresh (B,H,W) float32 tensor) or the caller's contiguous (B,H,W) float32 CUDA tensor for the per-pixel values; with a map the result is
+    (means, map).  out: the caller's contiguous (B,) float64 CUDA tensor.  The means are the same bits with and without a map, at every batch size
+    and on every stream."""
+    _cuda(a, b)
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
+        raise ValueError("image_ciede2000: the two images differ in shape, dtype or device: %s %s against %s %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    if a.dim() != 4 or a.shape[3] != 3 or a.dtype != torch.uint8 or min(a.shape) < 1:
+        raise ValueError("image_ciede2000 needs (B,H,W,3) uint8 images, got %s %s" % (tuple(a.shape), a.dtype))
+    B, H, W, _ = a.shape
+    lib = _lib.load()
+    nbytes = lib.cfen_ciede2000_bytes(B, H, W)
+    if nbytes == 0:
+        raise ValueError("image_ciede2000: %d images of %d x %d are outside the limits (B <= 65535, H, W <= 65536)" % (B, H, W))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+    if map is True:
+        map = torch.empty(B, H, W, dtype=torch.float32, device=a.device)
+    elif map is not None:
+        map = _out(map, (B, H, W), torch.float32, a.device, "image_ciede2000 (map)")
+    out = _out(out, (B,), torch.float64, a.device, "image_ciede2000")
+    check(lib.cfen_ciede2000_u8(ptr(a), ptr(b), B, H, W, ptr(_srgb_table(a.device)), ptr(scratch), ptr(map), ptr(out), current_stream()), "image_ciede2000")
+    return out if map is None else (out, map)      # (scratch goes back to torch's allocator on the stream it was used on)
+
+
 def png_deflate(images, out=None, out_lengths=None, workspace=None):
     """cfen_png_deflate: contiguous (B,H,W,3) uint8 CUDA images -> (slab, lengths): slab (B, out_stride) uint8 holds image b's finished zlib
     stream (the IDAT payload of an 8-bit RGB PNG, png.assemble adds the container) in slab[b, :lengths[b]]; lengths (B,) int32.  The candidate

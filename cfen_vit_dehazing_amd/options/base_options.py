@@ -123,6 +123,10 @@ class BaseOptions():
                        help='(extension) --eval: the columns of metrics.csv, psnr,ssim (default) or psnr,ssim,msssim. msssim is the reference\'s '
                             'pytorch_msssim.msssim (five levels of 2 x 2 means, normalize=None: nan where a level is anticorrelated), scored on the device '
                             'in the same call; every image must be at least 176 pixels on a side')
+        p.add_argument('--eval_ciede2000', action='store_true',
+                       help='(extension) --eval: a last column ciede2000 in metrics.csv, the mean CIEDE2000 colour difference (Sharma, Wu and Dalal 2005, '
+                            'kL = kC = kH = 1) of the written bytes against the ground truth, both read as sRGB; scored on the device in one more call '
+                            'per batch')
         p.add_argument('--gt_dir', type=str, default=None,
                        help='(extension) --eval: folder of ground-truth images, paired by stem or by the stem up to its first "_" (default <dataroot>/clear)')
         p.add_argument('--patch_dim', type=int, default=2)
@@ -202,6 +206,8 @@ class BaseOptions():
         eval_metrics_given = getattr(opt, 'eval_metrics', None) is not None
         if eval_metrics_given and not getattr(opt, 'eval', False):
             raise ValueError('--eval_metrics names the columns of --eval\'s metrics.csv: it needs --eval')
+        if getattr(opt, 'eval_ciede2000', False) and not getattr(opt, 'eval', False):
+            raise ValueError('--eval_ciede2000 adds a column to --eval\'s metrics.csv: it needs --eval')
         from .. import metrics as _metrics
         opt.eval_metrics = ','.join(_metrics.parse_columns(opt.eval_metrics if eval_metrics_given else 'psnr,ssim'))
         if not -1 <= opt.png_compress_level <= 9:
@@ -222,6 +228,8 @@ class BaseOptions():
             args = {k: v for k, v in args.items() if k not in ('eval', 'gt_dir')}      # a run without --eval prints and records what it always did
         if not eval_metrics_given:
             args = {k: v for k, v in args.items() if k != 'eval_metrics'}              # ... and one without --eval_metrics, with --eval or not
+        if not getattr(opt, 'eval_ciede2000', False):
+            args = {k: v for k, v in args.items() if k != 'eval_ciede2000'}            # ... and one without --eval_ciede2000
         if not getattr(opt, 'gpu_png', False):
             args = {k: v for k, v in args.items() if k != 'gpu_png'}                   # ... and so does one without --gpu_png
         if not getattr(opt, 'self_ensemble', False):

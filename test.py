@@ -7,7 +7,7 @@
 Loads checkpoints/<name>/<which_epoch>_net_G.pth (the reference's own file format), runs the HIP generator on
 every image of <dataroot>/hazy and writes results/<name>/<phase>_<which_epoch>/images/<stem>_fake_A.png.
 With --eval every image is also scored against <dataroot>/clear (PSNR, SSIM) into results/<name>/<phase>_<which_epoch>/metrics.csv;
---eval_metrics psnr,ssim,msssim adds an MS-SSIM column.
+--eval_metrics psnr,ssim,msssim adds an MS-SSIM column, --eval_ciede2000 a last column with the mean CIEDE2000 colour difference.
 """
 import logging
 import os
@@ -175,6 +175,8 @@ if __name__ == '__main__':
         from cfen_vit_dehazing_amd import metrics as _metrics
         rows = [(os.path.basename(r[0]),) + tuple(r[1:]) for r in model.current_metrics()]
         columns = tuple(opt.eval_metrics.split(','))           # --eval_metrics: ('psnr', 'ssim') unless it adds msssim
+        if getattr(opt, 'eval_ciede2000', False):
+            columns += (_metrics.CIEDE_COLUMN,)                # --eval_ciede2000: the last column
         if opt.dist_world > 1:
             import torch.distributed as dist
             gathered = [None] * opt.dist_world if opt.dist_rank == 0 else None
