@@ -53,6 +53,34 @@ def sample_idx(name, numel, n=512):
     return torch.randint(0, numel, (n,), generator=g)
 
 
+def gpu_stages(net, z):
+    """every stage but the tails of the v3 / v5 net's last forward, by fixture stage name"""
+    st = {}
+    xf = net.stage("ds_conv_e01")
+    for n in [str(s) for s in z["stage_names"]]:
+        if n.startswith("tail_"):
+            continue
+        t = net.stage(n)
+        if n.startswith("lgcat_conv_d01"):
+            t = t - xf                      # the plan folds `+ xf` (v3:696,852,1008) into this stage's epilogue
+        st[n] = t
+    return st
+
+
+def _cfs_stages(net, z):
+    """gpu_stages for the sibling generators (cfs / crs run level 1 on the head's own output)"""
+    st = {}
+    xf = net.stage("head" if net.cfg.full_res else "ds_conv_e01")
+    for n in [str(s) for s in z["stage_names"]]:
+        if n.startswith("tail_"):
+            continue
+        t = net.stage(n)
+        if n.startswith("lgcat_conv_d01"):
+            t = t - xf                      # `+ xf` (cfs:669,823,977) rides on this stage's epilogue
+        st[n] = t
+    return st
+
+
 def check_stages(z, stages, tol, rel_sum=1e-4):
     """Compare a dict of stage tensors (NCHW, CPU) against the fixture's samples and checksums."""
     worst = 0.0
@@ -67,6 +95,20 @@ def check_stages(z, stages, tol, rel_sum=1e-4):
         got_abs = float(t.double().abs().sum())
         assert abs(got_abs - ref_abs) <= rel_sum * ref_abs + 1e-6, "stage %s abs-sum %.6f vs %.6f" % (n, got_abs, ref_abs)
     return worst
+
+
+# ---- the fp16 stage bar (tools/gen_fp16_stage_model.py -> golden/fp16_stage_model.json) ----
+# One number for every stage and fixture: the fp16 plan may sit this many times further from the exact result than the rounding model does.  3 = the kernels
+# sum in another order than the model's exact sums (and in fp32, the model in float64), the fused kernels round at fewer points than the unfused plan the model
+# follows, and a maximum over 512 samples scatters by tens of percent between two realisations of the same noise.  It is a bar on the model: a stage that exceeds
+# it is a missing rounding point of the model or a kernel that loses accuracy, never a reason to raise it.
+FP16_STAGE_MARGIN = 3.0
+
+
+def fp16_stage_model():
+    import json
+    with open(os.path.join(GOLDEN, "fp16_stage_model.json")) as f:
+        return json.load(f)
 
 
 def check_outputs(z, outs, tol):
