@@ -156,6 +156,12 @@ COLORDIFF_SIGNATURES = {
     "cfen_ciede2000_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
+# every symbol include/cfen_noref.h declares: the no-reference statistics extension, bound beside the other four
+NOREF_SIGNATURES = {
+    "cfen_noref_bytes": (c_size_t, [_I, _I, _I, _I]),
+    "cfen_noref_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -169,7 +175,7 @@ def load():
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()) + \
-            list(COLORDIFF_SIGNATURES.items()):
+            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

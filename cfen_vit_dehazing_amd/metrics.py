@@ -13,7 +13,10 @@ Definition (fixed; include/cfen_hip.h has the long form).  Both images are score
         definition (include/cfen_colordiff.h has the long form).  uint8 images only; its own flag --eval_ciede2000, not a name of --eval_metrics.
 Images under 11 x 11 (MS-SSIM: under 176 x 176) are refused: the reference shrinks its window there, this project does not follow it.
 
-CUDA tensors only; there is no CPU fallback.  `format_csv` / `summarize` are the text side of test.py --eval."""
+CUDA tensors only; there is no CPU fallback.  `format_csv` / `summarize` are the text side of test.py --eval.
+
+Without ground truth (test.py --eval_noref, at the end of this file): statistics of the hazy input and of the dehazed output side by side, from
+ops.image_noref (csrc/k_noref.hip; include/cfen_noref.h has the long form)."""
 import math
 
 CSV_HEADER = "image,psnr,ssim"
@@ -167,3 +170,95 @@ def summary_line_columns(rows, columns):
     if CIEDE_COLUMN in columns:
         line += ", mean CIEDE2000 %.4f" % summarize_columns(rows, columns)["ciede2000_mean"]
     return line
+
+
+# ---- --eval_noref: statistics of the hazy input and the dehazed output, no ground truth (include/cfen_noref.h has the long form) ----------------
+# Per image of the pair, from the luma Y = (77 R + 150 G + 29 B + 128) >> 8:
+#   dark          mean of the dark channel (He, Sun and Tang 2009: min of min(R, G, B) over a (2 r + 1)^2 window clipped to the image) / 255
+#   entropy       -sum p log2 p over the non-empty bins of the 256-bin histogram of Y, in bits
+#   avg_gradient  mean over the (H - 1)(W - 1) positions of sqrt((dx^2 + dy^2) / 2), forward differences of Y on the 0..255 scale; nan without one
+#   contrast      population standard deviation of Y / 255
+# and for the pair: saturated, the share of pixels with Y_out in {0, 255} whose Y_hazy is not (sigma of Hautiere et al. 2008).
+NOREF_COLUMNS = ("dark_in", "dark_out", "entropy_in", "entropy_out", "avg_gradient_in", "avg_gradient_out", "contrast_in", "contrast_out", "saturated")
+NOREF_CSV_HEADER = "image," + ",".join(NOREF_COLUMNS)
+NOREF_MAX_RADIUS = 16
+
+
+def _noref_side(cnt, grad_sum, H, W):
+    """(dark, entropy, avg_gradient, contrast) of one side from its 259 integers and its gradient sum"""
+    n = H * W
+    hist = [int(c) for c in cnt[:256]]
+    if sum(hist) != n:
+        raise ValueError("noref_from_stats: the histogram holds %d pixels, the image %d x %d" % (sum(hist), H, W))
+    dark = int(cnt[256]) / (255.0 * n)
+    s = 0.0
+    for c in hist:
+        if c:
+            s += (c / n) * math.log2(c / n)
+    s1 = sum(v * c for v, c in enumerate(hist))
+    s2 = sum(v * v * c for v, c in enumerate(hist))
+    contrast = math.sqrt((n * s2 - s1 * s1) / float(n * n)) / 255.0          # exact integers up to the one division
+    positions = (H - 1) * (W - 1)
+    return dark, 0.0 - s, (float(grad_sum) / positions if positions > 0 else float("nan")), contrast
+
+
+def noref_from_stats(counts, grad, H, W):
+    """the device's raw statistics -> [(dark_in, dark_out, entropy_in, entropy_out, avg_gradient_in, avg_gradient_out, contrast_in, contrast_out,
+    saturated), ...] per image, Python floats in the order of NOREF_COLUMNS.  counts: (B,2,259) integers, grad: (B,2) floats (tensors, arrays
+    or nested lists: ops.image_noref's results after .cpu()); float64 on the host, the way msssim_from_levels finishes MS-SSIM"""
+    counts = counts.tolist() if hasattr(counts, "tolist") else counts
+    grad = grad.tolist() if hasattr(grad, "tolist") else grad
+    rows = []
+    for c, g in zip(counts, grad):
+        a, b = _noref_side(c[0], g[0], H, W), _noref_side(c[1], g[1], H, W)
+        rows.append((a[0], b[0], a[1], b[1], a[2], b[2], a[3], b[3], int(c[1][257]) / float(H * W)))
+    return rows
+
+
+def noref(hazy, out, radius=7):
+    """[NOREF_COLUMNS row, ...] per image pair.  hazy, out: (B,H,W,3) / (H,W,3) uint8 CUDA tensors of equal shape.  One device call (two
+    launches) and one copy of B * 4160 bytes back."""
+    import torch
+    from . import ops
+    if not isinstance(hazy, torch.Tensor) or not isinstance(out, torch.Tensor) or not hazy.is_cuda or not out.is_cuda:
+        raise ValueError("noref needs CUDA tensors; there is no CPU fallback")
+    counts, grad = ops.image_noref(hazy.contiguous(), out.contiguous(), radius)
+    B = counts.shape[0]
+    H, W = (hazy.shape[0], hazy.shape[1]) if hazy.dim() == 3 else (hazy.shape[1], hazy.shape[2])
+    # one copy back: the doubles travel as their bit patterns beside the integers
+    host = torch.cat([counts.view(B, -1), grad.view(torch.int64)], dim=1).cpu()
+    return noref_from_stats(host[:, :518].view(B, 2, 259), host[:, 518:].contiguous().view(torch.float64), int(H), int(W))
+
+
+def bytes_from_normalized(x):
+    """the loader's normalised floats (B,3,H,W), (v / 255 - 0.5) / 0.5, back to the decoded bytes (B,H,W,3) uint8, by ROUNDING: the float chain
+    lands within 1e-4 of v, and truncating (util.tensor2im) can come back one level low"""
+    import torch
+    return ((x.float() * 0.5 + 0.5) * 255.0).round().clamp(0.0, 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def format_noref_csv(rows):
+    """[(image, *NOREF_COLUMNS values), ...] -> the text of noref.csv: header, then %.6f values, one row per image"""
+    lines = [NOREF_CSV_HEADER]
+    for r in rows:
+        if len(r) != 1 + len(NOREF_COLUMNS):
+            raise ValueError("format_noref_csv: a row has %d values for %d columns" % (len(r) - 1, len(NOREF_COLUMNS)))
+        lines.append(",".join([str(r[0])] + ["%.6f" % v for v in r[1:]]))
+    return "\n".join(lines) + "\n"
+
+
+def summarize_noref(rows):
+    """{column + '_mean': mean over the rows that are not nan (nan when there is none)} and 'images'"""
+    s = {"images": len(rows)}
+    for i, name in enumerate(NOREF_COLUMNS):
+        good = [r[1 + i] for r in rows if not math.isnan(r[1 + i])]
+        s[name + "_mean"] = sum(good) / len(good) if good else float("nan")
+    return s
+
+
+def noref_summary_line(rows):
+    """the one line test.py --eval_noref prints (the contrast column is in the csv only)"""
+    s = summarize_noref(rows)
+    return ("noref: %d images, mean dark channel %.6f -> %.6f, mean entropy %.4f -> %.4f, mean avg gradient %.4f -> %.4f, mean saturated %.6f"
+            % (s["images"], s["dark_in_mean"], s["dark_out_mean"], s["entropy_in_mean"], s["entropy_out_mean"],
+               s["avg_gradient_in_mean"], s["avg_gradient_out_mean"], s["saturated_mean"]))

@@ -88,6 +88,10 @@ class DECHLGVIT(BaseModel):
         self._metrics = {}
         self._eval_msssim = self._eval and 'msssim' in (getattr(opt, 'eval_metrics', None) or '').split(',')      # --eval_metrics psnr,ssim,msssim
         self._eval_ciede = self._eval and bool(getattr(opt, 'eval_ciede2000', False))      # --eval_ciede2000: one more column, one more device call
+        # --eval_noref: statistics of the hazy bytes and the written bytes side by side, no ground truth (metrics.noref); a table of its own
+        self._noref = bool(getattr(opt, 'eval_noref', False))
+        self._noref_radius = 7 if getattr(opt, 'noref_radius', None) is None else int(opt.noref_radius)
+        self._noref_rows = {}
         # --self_ensemble: every image (or tile) runs as its eight flips / transposes and the outputs are averaged (ensemble.py); like --tile outside the guard
         self._x8 = bool(getattr(opt, 'self_ensemble', False))
         # --fit: every image is resampled to the generator's size on the device, runs through the plain branch of forward() -- the fp32 guard included --
@@ -111,13 +115,37 @@ class DECHLGVIT(BaseModel):
         BaseModel.test(self, opt)
         if getattr(self, '_eval', False):
             self._score()
+        if getattr(self, '_noref', False):
+            self._score_noref()
 
-    def _score(self):
-        from .. import metrics, ops
+    def _out_bytes(self):
+        """fake_A as the bytes save_images will write"""
+        from .. import ops
         out = self.fake_A
         if out.dtype != torch.uint8:
             # float outputs (no u8 output mode, or the fp32 side of a failed half guard): the bytes save_images will write, from the same device pass
             out = torch.stack([ops.tensor2im_u8(out[b].float().contiguous()) for b in range(out.shape[0])])
+        return out
+
+    def _score_noref(self):
+        """--eval_noref: the decoded hazy bytes at the output's size against the bytes that go into the fake_A PNG"""
+        from .. import metrics
+        out = self._out_bytes()
+        hazy = self._net_in                       # what the loader handed over: the decoded bytes (--u8_input, --fit: the original), or normalised floats
+        if hazy.dtype != torch.uint8:
+            hazy = metrics.bytes_from_normalized(hazy)
+        if tuple(hazy.shape) != tuple(out.shape):
+            raise ValueError('--eval_noref: the hazy image %s is %s but its output is %s' % (self.image_paths[0], tuple(hazy.shape[1:3]), tuple(out.shape[1:3])))
+        for path, row in zip(self.image_paths, metrics.noref(hazy, out, self._noref_radius)):
+            self._noref_rows[path] = row          # an image run again (redone in fp32 after a failed half guard) replaces its row, in place
+
+    def current_noref(self):
+        """[(hazy image path, *metrics.NOREF_COLUMNS values), ...] of every image scored so far under --eval_noref, in the order they first ran"""
+        return [(path,) + tuple(row) for path, row in getattr(self, '_noref_rows', {}).items()]
+
+    def _score(self):
+        from .. import metrics
+        out = self._out_bytes()
         gt = getattr(self, '_gt', None)
         if gt is None:
             raise RuntimeError('--eval: the dataset handed over no ground truth (key A) for %s' % (list(self.image_paths),))
@@ -161,6 +189,9 @@ class DECHLGVIT(BaseModel):
         [self.fake_R, self.fake_S, self.fake_A] = g['out']
         if getattr(self, '_eval', False):
             self._score()
+        if getattr(self, '_noref', False):
+            self._net_in = g['net_in']
+            self._score_noref()
 
     def current_metrics(self):
         """[(hazy image path, psnr, ssim), ...] of every image scored so far, in the order they first ran; with --eval_metrics psnr,ssim,msssim

@@ -663,6 +663,71 @@ def image_ciede2000(a, b, map=None, out=None):
     return out if map is None else (out, map)      # (scratch goes back to torch's allocator on the stream it was used on)
 
 
+NOREF_TILE_W, NOREF_TILE_H = 64, 64      # CFEN_NOREF_TILE_W / _H of include/cfen_noref.h: one workgroup, one scratch record, per tile
+NOREF_RECORD_BYTES = 2080                 # CFEN_NOREF_RECORD_BYTES
+NOREF_MAX_RADIUS = 16                     # CFEN_NOREF_MAX_RADIUS
+
+
+def _noref_images(what, *images):
+    _cuda(*images)
+    first = images[0]
+    for t in images:
+        if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8 or min(t.shape) < 1:
+            raise ValueError("%s needs (B,H,W,3) uint8 images, got %s %s" % (what, tuple(t.shape), t.dtype))
+        if t.shape != first.shape or t.device != first.device:
+            raise ValueError("%s: the two images differ in shape or device: %s against %s" % (what, tuple(first.shape), tuple(t.shape)))
+
+
+def image_noref(hazy, out, radius=7, maps=False):
+    """cfen_noref_u8 (include/cfen_noref.h): the raw no-reference statistics of B pairs (hazy input, dehazed output), as CUDA tensors.
+
+    hazy, out: (B,H,W,3) uint8 CUDA tensors of equal shape; an image without the batch dimension is taken as a batch of one.  radius: the dark
+    channel's window is (2 radius + 1)^2, 0 .. 16.  Returns (counts, grad): counts (B,2,259) int64 -- per side (0 hazy, 1 out) the 256 bins of
+    the luma histogram, dark_sum, the saturation count (side 0: sat_in, side 1: sat_new) and a reserved 0 -- and grad (B,2) float64, the
+    gradient sums.  With maps=True the result is (counts, grad, dark_hazy, dark_out), the two (B,H,W) uint8 dark-channel maps.  The same bits
+    with and without maps, at every batch size and on every stream; metrics.noref_from_stats turns the statistics into scores."""
+    if hazy.dim() == 3 and out.dim() == 3:
+        hazy, out = hazy[None], out[None]
+    _noref_images("image_noref", hazy, out)
+    B, H, W, _ = hazy.shape
+    lib = _lib.load()
+    nbytes = lib.cfen_noref_bytes(B, H, W, int(radius))
+    if nbytes == 0:
+        raise ValueError("image_noref: %d images of %d x %d at radius %s are outside the limits (B <= 65535, H, W <= 65536, radius 0 .. %d)"
+                         % (B, H, W, radius, NOREF_MAX_RADIUS))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=hazy.device)
+    counts = torch.empty(B, 2, 259, dtype=torch.int64, device=hazy.device)
+    grad = torch.empty(B, 2, dtype=torch.float64, device=hazy.device)
+    d0 = torch.empty(B, H, W, dtype=torch.uint8, device=hazy.device) if maps else None
+    d1 = torch.empty(B, H, W, dtype=torch.uint8, device=hazy.device) if maps else None
+    check(lib.cfen_noref_u8(ptr(hazy), ptr(out), B, H, W, int(radius), ptr(scratch), ptr(counts), ptr(grad), ptr(d0), ptr(d1), current_stream()),
+          "image_noref")
+    return (counts, grad, d0, d1) if maps else (counts, grad)      # (scratch goes back to torch's allocator on the stream it was used on)
+
+
+def dark_channel_u8(images, radius=7):
+    """the dark channel (He, Sun and Tang 2009) of (B,H,W,3) uint8 CUDA images as a (B,H,W) uint8 CUDA tensor: per pixel the minimum of
+    min(R, G, B) over the (2 radius + 1)^2 window clipped to the image (cfen_noref_u8 with the same images on both sides; an (H,W,3) image
+    gives an (H,W) map)"""
+    single = images.dim() == 3
+    if single:
+        images = images[None]
+    _noref_images("dark_channel_u8", images)
+    B, H, W, _ = images.shape
+    lib = _lib.load()
+    nbytes = lib.cfen_noref_bytes(B, H, W, int(radius))
+    if nbytes == 0:
+        raise ValueError("dark_channel_u8: %d images of %d x %d at radius %s are outside the limits (B <= 65535, H, W <= 65536, radius 0 .. %d)"
+                         % (B, H, W, radius, NOREF_MAX_RADIUS))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=images.device)
+    counts = torch.empty(B, 2, 259, dtype=torch.int64, device=images.device)
+    grad = torch.empty(B, 2, dtype=torch.float64, device=images.device)
+    dark = torch.empty(B, H, W, dtype=torch.uint8, device=images.device)
+    check(lib.cfen_noref_u8(ptr(images), ptr(images), B, H, W, int(radius), ptr(scratch), ptr(counts), ptr(grad), ptr(dark), None, current_stream()),
+          "dark_channel_u8")
+    return dark[0] if single else dark
+
+
 def png_deflate(images, out=None, out_lengths=None, workspace=None):
     """cfen_png_deflate: contiguous (B,H,W,3) uint8 CUDA images -> (slab, lengths): slab (B, out_stride) uint8 holds image b's finished zlib
     stream (the IDAT payload of an 8-bit RGB PNG, png.assemble adds the container) in slab[b, :lengths[b]]; lengths (B,) int32.  The candidate

@@ -127,6 +127,13 @@ class BaseOptions():
                        help='(extension) --eval: a last column ciede2000 in metrics.csv, the mean CIEDE2000 colour difference (Sharma, Wu and Dalal 2005, '
                             'kL = kC = kH = 1) of the written bytes against the ground truth, both read as sRGB; scored on the device in one more call '
                             'per batch')
+        p.add_argument('--eval_noref', action='store_true',
+                       help='(extension) score without ground truth: statistics of every hazy image and of its dehazed output side by side -- mean '
+                            'dark channel (He, Sun and Tang 2009), entropy, average gradient and contrast of the luma, and the share of newly '
+                            'saturated pixels (sigma of Hautiere et al. 2008) -- from the very bytes written to the PNG, on the device, into '
+                            'results/<name>/<phase>_<epoch>/noref.csv; needs --sb and --in_flight 1, does not need --eval, clear/ or --gt_dir')
+        p.add_argument('--noref_radius', type=int, default=None,
+                       help='(extension) --eval_noref: radius of the dark channel\'s (2 r + 1)^2 window, 0 .. 16 (default 7: He, Sun and Tang\'s 15 x 15)')
         p.add_argument('--gt_dir', type=str, default=None,
                        help='(extension) --eval: folder of ground-truth images, paired by stem or by the stem up to its first "_" (default <dataroot>/clear)')
         p.add_argument('--patch_dim', type=int, default=2)
@@ -208,8 +215,21 @@ class BaseOptions():
             raise ValueError('--eval_metrics names the columns of --eval\'s metrics.csv: it needs --eval')
         if getattr(opt, 'eval_ciede2000', False) and not getattr(opt, 'eval', False):
             raise ValueError('--eval_ciede2000 adds a column to --eval\'s metrics.csv: it needs --eval')
+        noref_radius_given = getattr(opt, 'noref_radius', None) is not None
+        if noref_radius_given and not getattr(opt, 'eval_noref', False):
+            raise ValueError('--noref_radius is the window of --eval_noref\'s dark channel: it needs --eval_noref')
+        if getattr(opt, 'eval_noref', False):
+            if opt.in_flight != 1:
+                raise ValueError('--eval_noref scores the images of the sequential loop: it needs --in_flight 1 (got --in_flight %d); the pipelined '
+                                 'driver does not compute metrics' % opt.in_flight)
+            if not opt.sb:
+                raise ValueError('--eval_noref needs --sb: without it the images are sampled randomly (dec_vit_data.py:51-58) and noref.csv would '
+                                 'not cover the dataset in order')
+            if noref_radius_given and not 0 <= opt.noref_radius <= 16:
+                raise ValueError('--eval_noref: --noref_radius must be in 0 .. 16 (got --noref_radius %d)' % opt.noref_radius)
+        opt.noref_radius = opt.noref_radius if noref_radius_given else 7
         from .. import metrics as _metrics
-        opt.eval_metrics = ','.join(_metrics.parse_columns(opt.eval_metrics if eval_metrics_given else 'psnr,ssim'))
+        opt.eval_metrics =','.join(_metrics.parse_columns(opt.eval_metrics if eval_metrics_given else 'psnr,ssim'))
         if not -1 <= opt.png_compress_level <= 9:
             raise ValueError('--png_compress_level must be -1 (PIL default) or 0..9')
         from .. import png as _png
@@ -230,6 +250,8 @@ class BaseOptions():
             args = {k: v for k, v in args.items() if k != 'eval_metrics'}              # ... and one without --eval_metrics, with --eval or not
         if not getattr(opt, 'eval_ciede2000', False):
             args = {k: v for k, v in args.items() if k != 'eval_ciede2000'}            # ... and one without --eval_ciede2000
+        if not getattr(opt, 'eval_noref', False):
+            args = {k: v for k, v in args.items() if k not in ('eval_noref', 'noref_radius')}      # ... and one without --eval_noref
         if not getattr(opt, 'gpu_png', False):
             args = {k: v for k, v in args.items() if k != 'gpu_png'}                   # ... and so does one without --gpu_png
         if not getattr(opt, 'self_ensemble', False):

@@ -8,6 +8,8 @@ Loads checkpoints/<name>/<which_epoch>_net_G.pth (the reference's own file forma
 every image of <dataroot>/hazy and writes results/<name>/<phase>_<which_epoch>/images/<stem>_fake_A.png.
 With --eval every image is also scored against <dataroot>/clear (PSNR, SSIM) into results/<name>/<phase>_<which_epoch>/metrics.csv;
 --eval_metrics psnr,ssim,msssim adds an MS-SSIM column, --eval_ciede2000 a last column with the mean CIEDE2000 colour difference.
+With --eval_noref (no ground truth needed) the hazy input and the dehazed output are scored side by side -- dark channel, entropy, average
+gradient, contrast, newly saturated pixels -- into results/<name>/<phase>_<which_epoch>/noref.csv.
 """
 import logging
 import os
@@ -187,6 +189,21 @@ if __name__ == '__main__':
                 f.write(_metrics.format_csv(rows) if columns == ('psnr', 'ssim') else _metrics.format_csv_columns(rows, columns))
             print(_metrics.summary_line(rows) if columns == ('psnr', 'ssim') else _metrics.summary_line_columns(rows, columns))
             print('eval: wrote %s' % os.path.join(web_dir, 'metrics.csv'))
+    if getattr(opt, 'eval_noref', False):
+        # --eval_noref: statistics of every hazy image and its written output side by side, no ground truth (scored on the device after every test()):
+        # one noref.csv in dataset order, gathered by rank 0 the way metrics.csv is
+        from cfen_vit_dehazing_amd import metrics as _metrics
+        rows = [(os.path.basename(r[0]),) + tuple(r[1:]) for r in model.current_noref()]
+        if opt.dist_world > 1:
+            import torch.distributed as dist
+            gathered = [None] * opt.dist_world if opt.dist_rank == 0 else None
+            dist.gather_object(rows, gathered, dst=0)
+            rows = [r for part in gathered for r in part] if opt.dist_rank == 0 else []
+        if opt.dist_rank == 0:
+            with open(os.path.join(web_dir, 'noref.csv'), 'w') as f:
+                f.write(_metrics.format_noref_csv(rows))
+            print(_metrics.noref_summary_line(rows))
+            print('noref: wrote %s' % os.path.join(web_dir, 'noref.csv'))
     if opt.dist_world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -1,0 +1,289 @@
+"""No-reference statistics on the device (cfen_noref_u8; ops.image_noref, ops.dark_channel_u8, metrics.noref, test.py --eval_noref) against the
+numpy restatement tests/noref_ref.py, and the second half of the ledger of include/cfen_noref.h.
+
+Bars:
+  counts, both dark-channel maps   bitwise equal to the restatement: they are integers.
+  grad                             |got - ref| <= 1e-9 |ref|.  Every term sqrt(0.5 (dx^2 + dy^2)) is correctly rounded on both sides, so only
+                                   the order of the fp64 additions differs: for N <= 2^20 non-negative terms that is bounded by about
+                                   N 2^-52 = 2.3e-10 relative.  One dropped position of the 97 x 131 case moves the sum by about 8e-5 relative.
+  csv values                       |csv - ref| <= 1e-6: the %.6f rounding (0.5e-6) plus 1e-9 of a gradient of at most 255."""
+import ctypes
+import inspect
+import os
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+from cfen_vit_dehazing_amd import _lib, metrics, ops
+from cfen_vit_dehazing_amd.manifest import generate_state_dict
+from cfen_vit_dehazing_amd.ops import NOREF_TILE_W, NOREF_TILE_H, NOREF_RECORD_BYTES
+import guarded
+import noref_ref as ref
+import test_hip_metrics as evalref                     # TINY, _run_cli, _dataset: the fixtures of the --eval CLI tests
+from test_noref_host import noref_header_functions
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+TOL_GRAD = 1e-9
+
+
+def dev(a):
+    return torch.from_numpy(np.array(a)).to(DEV)                 # a copy: the shared reference arrays are read-only
+
+
+def check(name, counts, grad, d0=None, d1=None):
+    hazy, out, r, want_counts, want_grad, want_maps = ref.case(name)
+    B = hazy.shape[0]
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (B, 2, 259) and grad.dtype == torch.float64 and tuple(grad.shape) == (B, 2)
+    got_counts, got_grad = counts.cpu().numpy(), grad.cpu().numpy()
+    rel = np.abs(got_grad - want_grad) / np.maximum(np.abs(want_grad), 1e-300)
+    rel[want_grad == 0] = np.abs(got_grad[want_grad == 0])
+    print("%s: counts differ in %d entries, grad max relative error %.3e" % (name, int((got_counts != want_counts).sum()), rel.max()))
+    assert np.array_equal(got_counts, want_counts)
+    assert (rel <= TOL_GRAD).all()
+    for got, want in ((d0, want_maps[0]), (d1, want_maps[1])):
+        if got is not None:
+            assert got.dtype == torch.uint8 and np.array_equal(got.cpu().numpy(), want)
+
+
+# ---- against the restatement -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(ref.CASES))
+def test_against_the_restatement(name):
+    hazy, out, r = ref.case(name)[:3]
+    th, to = dev(hazy), dev(out)
+    counts, grad, d0, d1 = ops.image_noref(th, to, radius=r, maps=True)
+    check(name, counts, grad, d0, d1)
+    # without the maps: the same bits; the dark channel alone: the same map
+    alone = ops.image_noref(th, to, radius=r)
+    assert len(alone) == 2 and torch.equal(alone[0], counts) and torch.equal(alone[1], grad)
+    assert torch.equal(ops.dark_channel_u8(to, radius=r), d1)
+
+
+def test_paths_the_cases_claim():
+    assert (NOREF_TILE_W, NOREF_TILE_H) == (ref.TILE_W, ref.TILE_H)
+    assert (17 * 67 * 3) % 4 == 1 and (97 * 131 * 3) % 4 == 1                                    # misaligned second images
+    q = _lib.load().cfen_noref_bytes
+    assert q(1, 16 * NOREF_TILE_H + 1, 16 * NOREF_TILE_W - 1, 7) == 272 * NOREF_RECORD_BYTES and 272 > 256      # more records than finish threads
+    assert q(1, 70, NOREF_TILE_W, 16) == 2 * NOREF_RECORD_BYTES and q(1, 70, NOREF_TILE_W + 1, 16) == 4 * NOREF_RECORD_BYTES
+    assert q(1, NOREF_TILE_H - 1, 70, 16) == 2 * NOREF_RECORD_BYTES and q(1, NOREF_TILE_H + 1, 70, 16) == 4 * NOREF_RECORD_BYTES
+    for name, (_, (B, H, W), r) in ref.CASES.items():
+        assert (H - 1) * (W - 1) <= 2 ** 20, name                                                # what the gradient bound assumes
+    hazy, out = ref.case("constant_r7")[:2]
+    assert len(np.unique(ref.luma(hazy))) == 1 and len(np.unique(ref.luma(out))) == 1             # every lane on one bin
+
+
+def test_dot_footprint_on_the_device():
+    for name, r in (("dot_r16", 16), ("dot_r7", 7)):
+        hazy = ref.case(name)[0]
+        d = ops.dark_channel_u8(dev(hazy), radius=r).cpu().numpy()
+        y, x = ref.DOT_AT[0]
+        n = 2 * r + 1
+        assert (d[0] == 0).sum() == n * n and (d[0][y - r:y + r + 1, x - r:x + r + 1] == 0).all()
+        assert (d[1] == 0).sum() == (r + 1) ** 2 and (d[1][:r + 1, :r + 1] == 0).all()          # clipped at the image's corner
+        single = ops.dark_channel_u8(dev(hazy[0]), radius=r)
+        assert tuple(single.shape) == hazy.shape[1:3] and np.array_equal(single.cpu().numpy(), d[0])
+
+
+def test_batch_stream_and_alignment_do_not_change_a_bit():
+    name = "3x17x67_r7"
+    hazy, out, r = ref.case(name)[:3]
+    th, to = dev(hazy), dev(out)
+    want = ops.image_noref(th, to, radius=r, maps=True)
+    check(name, *want)
+    one = [ops.image_noref(th[i:i + 1].clone(), to[i:i + 1].clone(), radius=r, maps=True) for i in range(3)]      # (each clone is aligned)
+    for k in range(4):
+        assert torch.equal(want[k], torch.cat([o[k] for o in one])), k
+    again = ops.image_noref(th, to, radius=r, maps=True)
+    assert all(torch.equal(a, b) for a, b in zip(want, again))
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        other = ops.image_noref(th, to, radius=r, maps=True)
+    side.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(want, other))
+    # views at byte offsets 1 .. 3 into a larger buffer, for either input
+    n = th.numel()
+    for off in (1, 2, 3):
+        bh, bo = torch.zeros(n + 4, dtype=torch.uint8, device=DEV), torch.zeros(n + 4, dtype=torch.uint8, device=DEV)
+        bh[off:off + n].copy_(th.flatten())
+        bo[off:off + n].copy_(to.flatten())
+        vh, vo = bh[off:off + n].view(th.shape), bo[off:off + n].view(to.shape)
+        assert vh.data_ptr() % 4 == off and vh.is_contiguous()
+        for pair in ((vh, vo), (vh, to), (th, vo)):                    # the choice is made per input
+            got = ops.image_noref(pair[0], pair[1], radius=r, maps=True)
+            assert all(torch.equal(a, b) for a, b in zip(want, got)), off
+
+
+# ---- guard bands and the header's ledger -----------------------------------------------------------------------------------------------------------
+def test_guard_bands_noref():
+    """both inputs between 0xff bands; scratch, counts, grad and the maps prefilled 0xff between random bands: no band changes, the results are
+    the unguarded call's, a zero prefill gives the same, and with NULL maps nothing but scratch, counts and grad is written"""
+    lib = _lib.load()
+    for name in ("3x17x67_r7", "2x97x131_r7", "w_tile+1_r16"):             # misaligned images and two tiles; 2 x 3 tiles; a 16-pixel halo over tile edges
+        hazy, out, r = ref.case(name)[:3]
+        B, H, W = hazy.shape[:3]
+        th, to = guarded.guarded_copy(dev(hazy)), guarded.guarded_copy(dev(out))
+        nbytes = lib.cfen_noref_bytes(B, H, W, r)
+        assert nbytes == B * -(-H // NOREF_TILE_H) * -(-W // NOREF_TILE_W) * NOREF_RECORD_BYTES
+        scratch = guarded.guarded_empty((nbytes // 8,), torch.int64, DEV, fill="ff")
+        counts = guarded.guarded_empty((B, 2, 259), torch.int64, DEV, fill="ff")
+        grad = guarded.guarded_empty((B, 2), torch.float64, DEV, fill="ff")
+        d0 = guarded.guarded_empty((B, H, W), torch.uint8, DEV, fill="zero")
+        d1 = guarded.guarded_empty((B, H, W), torch.uint8, DEV, fill="zero")
+        want = ops.image_noref(dev(hazy), dev(out), radius=r, maps=True)
+        for fill in ("ff", "zero", "random"):
+            for t in (scratch, counts, grad, d0, d1):
+                guarded.refill(t, fill)
+            _lib.check(lib.cfen_noref_u8(_lib.ptr(th), _lib.ptr(to), B, H, W, r, _lib.ptr(scratch), _lib.ptr(counts), _lib.ptr(grad), _lib.ptr(d0),
+                                         _lib.ptr(d1), _lib.current_stream()), "noref_u8")
+            torch.cuda.synchronize()
+            guarded.check_bands(th, to, scratch, counts, grad, d0, d1)
+            assert all(torch.equal(a, b) for a, b in zip(want, (counts, grad, d0, d1))), (name, fill)
+        for t in (scratch, counts, grad, d0, d1):
+            guarded.refill(t, "ff")
+        _lib.check(lib.cfen_noref_u8(_lib.ptr(th), _lib.ptr(to), B, H, W, r, _lib.ptr(scratch), _lib.ptr(counts), _lib.ptr(grad), None, None,
+                                     _lib.current_stream()), "noref_u8")
+        torch.cuda.synchronize()
+        guarded.check_bands(th, to, scratch, counts, grad, d0, d1)
+        assert torch.equal(counts, want[0]) and torch.equal(grad, want[1])
+        assert bool((guarded.raw_bytes(d0) == 255).all()) and bool((guarded.raw_bytes(d1) == 255).all())
+        check(name, counts, grad)
+
+
+def test_every_function_of_the_noref_header_is_guard_band_tested():
+    fns = noref_header_functions()
+    assert fns and sorted(fns) == sorted(_lib.NOREF_SIGNATURES)
+    body = inspect.getsource(test_guard_bands_noref)
+    for sym in fns:
+        assert "lib.%s(" % sym in body, "test_guard_bands_noref does not call %s" % sym
+
+
+# ---- refusals ------------------------------------------------------------------------------------------------------------------------------------------
+def test_argument_errors_launch_nothing():
+    lib = _lib.load()
+    B, H, W = 2, 3, 5
+    hazy, out = (dev(x) for x in ref.case("2x3x5_r7")[:2])
+    scratch = torch.full((B * NOREF_RECORD_BYTES // 8,), 7, dtype=torch.int64, device=DEV)
+    counts = torch.full((B, 2, 259), 7, dtype=torch.int64, device=DEV)
+    grad = torch.full((B + 1, 2), 7.0, dtype=torch.float64, device=DEV)
+    d0 = torch.full((B, H, W), 7, dtype=torch.uint8, device=DEV)
+    d1 = torch.full((B, H, W), 7, dtype=torch.uint8, device=DEV)
+    p, z = _lib.ptr, ctypes.c_void_p(0)
+    order = ("hazy", "out", "B", "H", "W", "radius", "scratch", "counts", "grad", "d0", "d1")
+    good = dict(hazy=p(hazy), out=p(out), B=B, H=H, W=W, radius=7, scratch=p(scratch), counts=p(counts), grad=p(grad), d0=p(d0), d1=p(d1))
+    bad = [(k, z, b"null pointer") for k in ("hazy", "out", "scratch", "counts", "grad")]
+    bad += [("B", 0, b"B = 0"), ("B", -1, b"B = -1"), ("B", 65536, b"B = 65536"), ("H", 0, b"H = 0"), ("W", 0, b"W = 0"), ("H", 65537, b"H = 65537"),
+            ("W", 65537, b"W = 65537"), ("H", -4, b"H = -4"), ("radius", -1, b"radius = -1"), ("radius", 17, b"radius = 17"),
+            ("scratch", ctypes.c_void_p(scratch.data_ptr() + 4), b"8-byte aligned"), ("counts", ctypes.c_void_p(counts.data_ptr() + 4), b"8-byte aligned"),
+            ("grad", ctypes.c_void_p(grad.data_ptr() + 4), b"8-byte aligned")]
+    for key, value, what in bad:
+        args = dict(good, **{key: value})
+        rc = lib.cfen_noref_u8(*[args[k] for k in order], _lib.current_stream())
+        err = lib.cfen_last_error()
+        assert rc == -1 and b"noref_u8" in err and what in err, (key, rc, err)
+    torch.cuda.synchronize()
+    assert all(bool((t == 7).all()) for t in (scratch, counts, grad, d0, d1))
+    _lib.check(lib.cfen_noref_u8(*[good[k] for k in order], _lib.current_stream()), "noref_u8")
+    torch.cuda.synchronize()
+    assert bool((counts[:, :, 258] == 0).all()) and bool((grad[B] == 7.0).all()) and bool((grad[:B] != 7.0).all())
+    check("2x3x5_r7", counts, grad[:B], d0, d1)
+
+
+def test_python_side_refusals_and_metrics_noref():
+    u = torch.zeros(1, 4, 6, 3, dtype=torch.uint8, device=DEV)
+    with pytest.raises(ValueError, match="differ"):
+        ops.image_noref(u, torch.zeros(1, 4, 7, 3, dtype=torch.uint8, device=DEV))
+    with pytest.raises(ValueError, match="uint8"):
+        ops.image_noref(u.float(), u.float())
+    with pytest.raises(ValueError, match=r"\(B,H,W,3\)"):
+        ops.image_noref(u[..., :2].contiguous(), u[..., :2].contiguous())
+    with pytest.raises(ValueError, match="contiguous"):
+        ops.image_noref(u.cpu(), u.cpu())
+    for r in (-1, 17):
+        with pytest.raises(ValueError, match="radius"):
+            ops.image_noref(u, u, radius=r)
+        with pytest.raises(ValueError, match="radius"):
+            ops.dark_channel_u8(u, radius=r)
+    with pytest.raises(ValueError, match="CUDA tensors"):
+        metrics.noref(u.cpu(), u.cpu())
+    counts, grad = ops.image_noref(u[0], u[0])                                                    # an image without the batch dimension
+    assert counts[0, :, 0].tolist() == [24, 24] and grad.tolist() == [[0.0, 0.0]]
+    hazy, out, r = ref.case("2x97x131_r7")[:3]
+    got = metrics.noref(dev(hazy), dev(out), radius=r)
+    want = ref.scores(hazy, out, r)
+    assert isinstance(got, list) and len(got) == 2 and all(isinstance(v, float) for row in got for v in row)
+    assert np.abs(np.array(got) - want).max() <= 1e-9 * 255
+
+
+# ---- CLI ---------------------------------------------------------------------------------------------------------------------------------------------
+NAME = "iid_hlgvit_crs_gd4_cfs_v3_eval"
+
+
+def _setup(tmp_path, size, seed, clear=False):
+    os.makedirs(tmp_path / "ckpt" / NAME)
+    torch.save(generate_state_dict(evalref.TINY, seed=0), tmp_path / "ckpt" / NAME / "32_net_G.pth")
+    data = tmp_path / "data"
+    pairs = evalref._dataset(data, size, seed=seed)
+    if not clear:
+        shutil.rmtree(data / "clear")                    # no ground truth anywhere: that is the point
+    return data, sorted(pairs)
+
+
+def _check_noref_csv(res, data, images, stdout, radius=7):
+    from PIL import Image
+    lines = open(res / "noref.csv").read().splitlines()
+    assert lines[0] == metrics.NOREF_CSV_HEADER and [l.split(",")[0] for l in lines[1:]] == images           # dataset order
+    rows = []
+    for line in lines[1:]:
+        image, values = line.split(",")[0], [float(v) for v in line.split(",")[1:]]
+        out = np.asarray(Image.open(res / "images" / (os.path.splitext(image)[0] + "_fake_A.png")).convert("RGB"))
+        hazy = np.asarray(Image.open(data / "hazy" / image).convert("RGB"))
+        assert out.shape == hazy.shape
+        want = ref.scores(hazy[None], out[None], radius)[0]
+        print("%s: csv %s\n   from the files: %s" % (image, values, want.tolist()))
+        assert np.abs(np.array(values) - want).max() <= 1e-6
+        rows.append((image,) + tuple(values))
+    summary = [l for l in stdout.splitlines() if l.startswith("noref: ") and "mean dark channel" in l]
+    assert len(summary) == 1 and summary[0].startswith("noref: %d images, mean dark channel %.6f -> %.6f, mean entropy "
+                                                       % (len(rows), sum(r[1] for r in rows) / len(rows), sum(r[2] for r in rows) / len(rows)))
+    assert "mean avg gradient" in summary[0] and "mean saturated" in summary[0]
+
+
+@pytest.mark.parametrize("mode", ["plain", "tile", "fit", "batch2", "packed_u8_half_x8_gpu_png"])
+def test_cli_eval_noref_scores_the_hazy_files_against_the_written_pngs(tmp_path, mode):
+    data, images = _setup(tmp_path, (128, 128) if mode in ("plain", "batch2") else (150, 201), seed=9)
+    extra = {"plain": [], "tile": ["--tile", "--tile_overlap", "16"], "fit": ["--fit"], "batch2": ["--batchSize", "2"],
+             # the other flags it composes with, in one run: uint8 hazy bytes from the loader, packed tiles, fp16, the ensemble, device PNGs
+             "packed_u8_half_x8_gpu_png": ["--tile", "--tile_overlap", "16", "--tile_pack", "2", "--u8_input", "--precision", "half", "--self_ensemble",
+                                           "--gpu_png"]}[mode]
+    r = evalref._run_cli(tmp_path, data, NAME, extra + ["--eval_noref"], "noref")
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "eval_noref: True" in r.stdout and "noref_radius: 7" in r.stdout
+    res = tmp_path / "res_noref" / NAME / "test_32"
+    assert not os.path.exists(res / "metrics.csv")
+    _check_noref_csv(res, data, images, r.stdout)
+
+
+def test_cli_eval_and_eval_noref_write_both_files_and_nothing_changes_without_the_flag(tmp_path):
+    data, images = _setup(tmp_path, (128, 128), seed=10, clear=True)
+    r = evalref._run_cli(tmp_path, data, NAME, ["--eval", "--eval_noref", "--noref_radius", "3"], "both")
+    assert r.returncode == 0, r.stdout[-3000:]
+    r2 = evalref._run_cli(tmp_path, data, NAME, ["--eval"], "eval")                 # the same command without the flag
+    assert r2.returncode == 0, r2.stdout[-3000:]
+    both, alone = tmp_path / "res_both" / NAME / "test_32", tmp_path / "res_eval" / NAME / "test_32"
+    assert open(both / "metrics.csv", "rb").read() == open(alone / "metrics.csv", "rb").read()
+    assert "noref_radius: 3" in r.stdout
+    _check_noref_csv(both, data, images, r.stdout, radius=3)
+    eval_lines = [[l for l in x.stdout.splitlines() if l.startswith("eval: ") and "mean PSNR" in l] for x in (r, r2)]
+    assert eval_lines[0] == eval_lines[1] and len(eval_lines[0]) == 1
+    # without the flag: no noref.csv, no line or option of it, the same PNG bytes
+    assert not os.path.exists(alone / "noref.csv")
+    keys = [l.split(":")[0] for l in r2.stdout.splitlines()]
+    assert "noref" not in keys and "eval_noref" not in keys and "noref_radius" not in keys
+    files = sorted(os.listdir(both / "images"))
+    assert files == sorted(os.listdir(alone / "images")) and len(files) == 3
+    for f in files:
+        assert open(both / "images" / f, "rb").read() == open(alone / "images" / f, "rb").read(), f
