@@ -162,6 +162,19 @@ NOREF_SIGNATURES = {
     "cfen_noref_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
+
+class YuvTableC(ctypes.Structure):
+    """cfen_yuv_table of include/cfen_yuv.h, passed by value: 9 coefficients in units of 2^-14, the luma offset, 6 reserved zeros"""
+    _fields_ = [("coef", ctypes.c_int32 * 9), ("luma_offset", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+# every symbol include/cfen_yuv.h declares: the YCbCr <-> RGB extension, bound beside the other five
+YUV_SIGNATURES = {
+    "cfen_yuv_frame_bytes": (c_size_t, [_I, _I, _I]),
+    "cfen_yuv_to_rgb_u8": (_I, [_P, c_size_t, _I, _I, _I, _I, YuvTableC, _P, _P]),
+    "cfen_rgb_to_yuv_u8": (_I, [_P, _I, _I, _I, _I, YuvTableC, _P, c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -175,7 +188,7 @@ def load():
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()) + \
-            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()):
+            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()) + list(YUV_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcfen_hip.so")
-SOURCES = ["k_gemm.hip", "k_attention.hip", "k_tokens.hip", "k_conv.hip", "k_conv_tile.hip", "k_mlp.hip", "k_embed.hip", "k_lvit.hip", "k_stream.hip", "k_gvit.hip", "k_head5.hip", "k_fuse.hip", "k_tail.hip", "k_tile.hip", "k_ensemble.hip", "k_resample.hip", "k_guided.hip", "k_metrics.hip", "k_colordiff.hip", "k_noref.hip", "k_png.hip", "k_dcn.hip", "k_dcn_bwd.hip", "cfen_api.cpp", "cfen_net.cpp", "cfen_tune.cpp"]
+SOURCES = ["k_gemm.hip", "k_attention.hip", "k_tokens.hip", "k_conv.hip", "k_conv_tile.hip", "k_mlp.hip", "k_embed.hip", "k_lvit.hip", "k_stream.hip", "k_gvit.hip", "k_head5.hip", "k_fuse.hip", "k_tail.hip", "k_tile.hip", "k_ensemble.hip", "k_resample.hip", "k_guided.hip", "k_metrics.hip", "k_colordiff.hip", "k_noref.hip", "k_yuv.hip", "k_png.hip", "k_dcn.hip", "k_dcn_bwd.hip", "cfen_api.cpp", "cfen_net.cpp", "cfen_tune.cpp"]
 # per-file codegen flags.  k_attention: the softmax is VALU bound -- drop fmaxf's NaN canonicalisation (no NaNs can
 # occur: masked scores are -1e30, not -inf) and let MFMA results land in VGPRs instead of AGPR + v_accvgpr_read.
 EXTRA_FLAGS = {"k_attention.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
@@ -33,10 +33,9 @@ def _newer(a, b):
     return not os.path.exists(b) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
-def check_no_packed_fp32(lib=LIB):
-    """Disassemble the device code of the linked library and count v_pk_{fma,mul,add}_f32 (see DEVICE_FLAGS: a performance choice,
-    CFEN_CXXFLAGS or another hipcc could silently undo it).  Returns the number of such instructions (0 = as intended), None
-    when llvm-objdump is not available."""
+def count_device_instructions(pattern, lib=LIB):
+    """Disassemble the device code of the linked library and count the instructions matching the regular expression `pattern`.  None when
+    llvm-objdump is not available."""
     import re
     import shutil
     import tempfile
@@ -53,10 +52,25 @@ def check_no_packed_fp32(lib=LIB):
         for f in sorted(os.listdir(tmp)):
             if "amdgcn" in f:
                 out = subprocess.run([objdump, "-d", os.path.join(tmp, f)], capture_output=True, text=True, check=False).stdout
-                n += len(re.findall(r"\bv_pk_(?:fma|mul|add)_f32\b", out))
+                n += len(re.findall(pattern, out))
         return n
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+def check_no_packed_fp32(lib=LIB):
+    """count v_pk_{fma,mul,add}_f32 in the linked library (see DEVICE_FLAGS: a performance choice, CFEN_CXXFLAGS or another hipcc could silently
+    undo it).  Returns the number of such instructions (0 = as intended), None when llvm-objdump is not available."""
+    return count_device_instructions(r"\bv_pk_(?:fma|mul|add)_f32\b", lib)
+
+
+def check_no_ashr_pk_u8(lib=LIB):
+    """count v_ashr_pk_u8_i32 in the linked library.  Unlike the packed-fp32 count this one is about CORRECTNESS: hipcc (ROCm 7.2) fuses shift +
+    clamp + packing of two bytes into this instruction and then ORs further bytes into the destination's upper half as if it were zero, and on
+    the MI355X byte 2 of such a dword came out wrong (csrc/k_yuv.hip, yv_dot).  No kernel here needs the instruction and the
+    shipped build holds none, so any occurrence -- the workaround undone by another compiler, or new code that packs bytes -- is reported by
+    build() and fails tests/test_yuv_host.py.  Returns the count (0 = as intended), None when llvm-objdump is not available."""
+    return count_device_instructions(r"\bv_ashr_pk_u8_i32\b", lib)
 
 
 def build(force=False, verbose=False, packed_fp32=False, lib=None, objdir=None):
@@ -72,6 +86,7 @@ def build(force=False, verbose=False, packed_fp32=False, lib=None, objdir=None):
     headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_guided.h"))
     headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_colordiff.h"))
     headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_noref.h"))
+    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_yuv.h"))
     headers.append(os.path.abspath(__file__))          # flags live here
     objs = []
     procs = []
@@ -107,6 +122,10 @@ def build(force=False, verbose=False, packed_fp32=False, lib=None, objdir=None):
             if n:
                 sys.stderr.write("note: libcfen_hip.so contains %d packed-fp32 VALU instructions (DEVICE_FLAGS overridden?): slower beside "
                                  "MFMAs, results unaffected\n" % n)
+        n = check_no_ashr_pk_u8(lib)
+        if n:
+            sys.stderr.write("WARNING: libcfen_hip.so contains %d v_ashr_pk_u8_i32 instructions: this compiler's byte packing around it gave wrong "
+                             "bytes on the MI355X (csrc/k_yuv.hip, yv_dot); run the GPU tests before trusting uint8 outputs\n" % n)
     return lib
 
 

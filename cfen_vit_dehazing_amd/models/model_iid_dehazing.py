@@ -127,6 +127,19 @@ class DECHLGVIT(BaseModel):
             out = torch.stack([ops.tensor2im_u8(out[b].float().contiguous()) for b in range(out.shape[0])])
         return out
 
+    # ---- what a driver other than test.py (video.py) needs from the model, without reaching into its state ---------------------------------------
+    def output_bytes(self):
+        """fake_A of the last test() as (B,H,W,3) uint8: the bytes save_images would write"""
+        return self._out_bytes()
+
+    def set_noref_scoring(self, on):
+        """--eval_noref: score inside test() (test.py) or leave it to the caller, who scores the same bytes itself"""
+        self._noref = bool(on)
+
+    def use_native_size_route(self):
+        """the inputs are of the generator's own size: take the plain branch of forward() whatever --fit / --tile asked for other sizes"""
+        self._fit = self._tile = False
+
     def _score_noref(self):
         """--eval_noref: the decoded hazy bytes at the output's size against the bytes that go into the fake_A PNG"""
         from .. import metrics

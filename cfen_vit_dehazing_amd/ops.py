@@ -6,6 +6,7 @@ is no PyTorch fallback.
 """
 import contextlib
 import ctypes
+import functools
 
 import torch
 
@@ -726,6 +727,88 @@ def dark_channel_u8(images, radius=7):
     check(lib.cfen_noref_u8(ptr(images), ptr(images), B, H, W, int(radius), ptr(scratch), ptr(counts), ptr(grad), ptr(dark), None, current_stream()),
           "dark_channel_u8")
     return dark[0] if single else dark
+
+
+def yuv_table(coef, oy):
+    """a cfen_yuv_table (include/cfen_yuv.h) from a (3,3) integer table of yuv.tables and its luma offset: passed to the kernels by value"""
+    t = _lib.YuvTableC()
+    flat = [int(v) for row in coef for v in row]
+    if len(flat) != 9:
+        raise ValueError("yuv_table needs a 3 x 3 table, got %d entries" % len(flat))
+    for k, v in enumerate(flat):
+        t.coef[k] = v
+    t.luma_offset = int(oy)
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def _yuv_table_for(matrix, full_range, inverse):
+    """the forward or inverse table of yuv.tables as a cfen_yuv_table, built once per (matrix, range, direction)"""
+    from . import yuv
+    fwd, inv, oy = yuv.tables(matrix, full_range)
+    return yuv_table(inv if inverse else fwd, oy)
+
+
+def _yuv_frames(what, frames, nbytes):
+    """a batch of frames as the kernels take it: (B, frame_bytes) uint8 on the device, rows `stride(0)` >= frame_bytes bytes apart, bytes of a row adjacent"""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[0] < 1 or \
+            frames.shape[1] != nbytes or (frames.stride(1) != 1 and nbytes > 1) or (frames.shape[0] > 1 and frames.stride(0) < nbytes):
+        raise ValueError("%s: frames must be a (B, %d) uint8 CUDA tensor whose rows are whole frames (unit stride inside a frame, frames at least "
+                         "a frame apart), got %s" % (what, nbytes, (tuple(frames.shape), frames.stride(), frames.dtype) if isinstance(frames, torch.Tensor)
+                                                     else type(frames)))
+    return max(int(frames.stride(0)), nbytes) if frames.shape[0] > 1 else nbytes
+
+
+def yuv_to_rgb_u8(frames, H, W, chroma, matrix="bt601", full_range=False, out=None):
+    """cfen_yuv_to_rgb_u8 (include/cfen_yuv.h): B planar YCbCr frames -- the FRAME payloads of a .y4m stream as they are, (B, frame_bytes) uint8,
+    rows any number >= frame_bytes of bytes apart, at any byte offset -- to (B,H,W,3) uint8 RGB.  A 1-D tensor is one frame and gives (H,W,3).
+    chroma: one of yuv.CHROMA ("420jpeg", "420mpeg2", "422", "444", "mono"); matrix, full_range: the integer table of yuv.tables.  One launch,
+    integer arithmetic, the same bits at every batch size, stride, alignment and stream."""
+    from . import yuv
+    code = yuv.chroma_code(chroma)
+    single = isinstance(frames, torch.Tensor) and frames.dim() == 1
+    if single:
+        frames = frames[None]
+    lib = _lib.load()
+    nbytes = lib.cfen_yuv_frame_bytes(int(H), int(W), code)
+    if nbytes == 0:
+        raise ValueError("yuv_to_rgb_u8: frames of %s x %s are outside the limits (H, W in 1 .. %d)" % (H, W, yuv.MAX_EDGE))
+    stride = _yuv_frames("yuv_to_rgb_u8", frames, nbytes)
+    B = frames.shape[0]
+    if out is not None and single:
+        out = out[None]
+    out = _out(out, (B, H, W, 3), torch.uint8, frames.device, "yuv_to_rgb_u8")
+    check(lib.cfen_yuv_to_rgb_u8(ptr(frames), stride, B, int(H), int(W), code, _yuv_table_for(matrix, bool(full_range), True), ptr(out), current_stream()),
+          "yuv_to_rgb_u8")
+    return out[0] if single else out
+
+
+def rgb_to_yuv_u8(rgb, chroma, matrix="bt601", full_range=False, out=None):
+    """cfen_rgb_to_yuv_u8: (B,H,W,3) uint8 CUDA images to B planar YCbCr frames, (B, frame_bytes) uint8 (an (H,W,3) image gives a 1-D frame).
+    out: the caller's (B, frame_bytes) tensor, rows at least a frame apart (a view into a larger buffer: the bytes between two frames are not
+    written).  The counterpart of yuv_to_rgb_u8 with the forward table of yuv.tables; chroma planes are filtered from the converted bytes."""
+    from . import yuv
+    code = yuv.chroma_code(chroma)
+    single = rgb.dim() == 3
+    if single:
+        rgb = rgb[None]
+    _cuda(rgb)
+    if rgb.dim() != 4 or rgb.shape[3] != 3 or rgb.dtype != torch.uint8 or min(rgb.shape) < 1:
+        raise ValueError("rgb_to_yuv_u8 needs (B,H,W,3) uint8 images, got %s %s" % (tuple(rgb.shape), rgb.dtype))
+    B, H, W, _ = rgb.shape
+    lib = _lib.load()
+    nbytes = lib.cfen_yuv_frame_bytes(H, W, code)
+    if nbytes == 0:
+        raise ValueError("rgb_to_yuv_u8: images of %d x %d are outside the limits (H, W in 1 .. %d)" % (H, W, yuv.MAX_EDGE))
+    if out is None:
+        out = torch.empty(B, nbytes, dtype=torch.uint8, device=rgb.device)
+    elif single and out.dim() == 1:
+        out = out[None]
+    stride = _yuv_frames("rgb_to_yuv_u8 (out)", out, nbytes)
+    if out.shape[0] != B or out.device != rgb.device:
+        raise ValueError("rgb_to_yuv_u8: out holds %d frames on %s for %d images on %s" % (out.shape[0], out.device, B, rgb.device))
+    check(lib.cfen_rgb_to_yuv_u8(ptr(rgb), B, H, W, code, _yuv_table_for(matrix, bool(full_range), False), ptr(out), stride, current_stream()), "rgb_to_yuv_u8")
+    return out[0] if single else out
 
 
 def png_deflate(images, out=None, out_lengths=None, workspace=None):

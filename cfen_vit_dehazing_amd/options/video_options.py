@@ -1,0 +1,75 @@
+"""Flags of dehaze_video.py: every flag of test.py (TestOptions, unchanged) plus the stream's own.  Differences from test.py, all stated here:
+  * --dataroot is not needed (there is no folder of images) and --sb is implied: frames are taken in order.
+  * --batchSize defaults to 8 frames per forward, and --tile takes any --batchSize: the tiles of a batch's frames are packed into common
+    forwards (hipnet.forward_tiled_many), which test.py reaches through --tile_pack.
+  * --u8_input is always on: the converted frames are bytes.
+  * --in_flight stays 1: the loop has its own reader and writer threads (--video_buffers).
+  * the options are recorded in <checkpoints_dir>/<name>/video_opt.txt; opt.txt, which test.py writes, is left as it was."""
+import os
+
+from .test_options import TestOptions
+
+
+class VideoOptions(TestOptions):
+    def initialize(self):
+        TestOptions.initialize(self)
+        p = self.parser
+        p.add_argument('--in', dest='video_in', required=True, help='the .y4m stream to dehaze: a path, or - for stdin')
+        p.add_argument('--out', dest='video_out', required=True, help='where the dehazed .y4m stream goes: a path, or - for stdout (everything printed then goes to stderr)')
+        p.add_argument('--video_matrix', default='auto', choices=('auto', 'bt601', 'bt709'),
+                       help='YCbCr matrix of the stream; auto: bt709 for frames of 720 rows or more, bt601 below (a y4m header does not say)')
+        p.add_argument('--video_range', default='auto', choices=('auto', 'limited', 'full'),
+                       help='sample range of the stream; auto: the XCOLORRANGE tag of the header, limited (16 .. 235) without one')
+        p.add_argument('--video_buffers', type=int, default=4, help='slots of the ring of pinned host buffers between the reader, the device and the writer (each holds a batch both ways)')
+        p.add_argument('--noref_csv', type=str, default=None, help='--eval_noref: where noref.csv goes (default: beside --out; required when --out is -)')
+        for a in p._actions:
+            if a.dest == 'dataroot':
+                a.required = False
+        p.set_defaults(batchSize=8, dataroot='')
+
+    def parse(self, argv=None):
+        import sys
+        if not self.initialized:
+            self.initialize()
+        argv = list(sys.argv[1:] if argv is None else argv)
+        first, _ = self.parser.parse_known_args(argv)
+        if first.batchSize < 1:
+            raise ValueError('--batchSize must be >= 1')
+        if first.video_buffers < 1:
+            raise ValueError('--video_buffers must be >= 1')
+        if first.in_flight != 1:
+            raise ValueError('dehaze_video.py has its own reader and writer threads (--video_buffers): --in_flight stays 1')
+        if first.eval_noref and first.video_out == '-' and not first.noref_csv:
+            raise ValueError('--eval_noref with --out -: say where noref.csv goes with --noref_csv PATH')
+        if first.noref_csv and not first.eval_noref:
+            raise ValueError('--noref_csv is where --eval_noref writes: it needs --eval_noref')
+        # test.py's own checks run on what test.py would be given: frames in order, and --tile there means one image per call.  What that parse
+        # prints and records is held back, corrected to the batch size this run really uses, and recorded in a file of its own: opt.txt stays
+        # what the last test.py run of the same --name wrote
+        import contextlib
+        import io
+        extra = ['--sb', '--u8_input'] + (['--batchSize', '1'] if first.tile else [])
+        opt_txt = os.path.join(first.checkpoints_dir, first.name + (('_' + first.suffix.format(**vars(first))) if first.suffix else ''), 'opt.txt')
+        before = open(opt_txt, 'rb').read() if os.path.exists(opt_txt) else None
+        held = io.StringIO()
+        with contextlib.redirect_stdout(held):
+            opt = TestOptions.parse(self, argv + extra)
+        opt.batchSize = first.batchSize
+        text = held.getvalue().replace('\nbatchSize: 1\n', '\nbatchSize: %d\n' % opt.batchSize) if first.tile else held.getvalue()
+        sys.stdout.write(text)
+        sys.stdout.flush()
+        if opt.dist_rank == 0:
+            try:
+                recorded = open(opt_txt).read()
+                if before is None:
+                    os.remove(opt_txt)
+                else:
+                    with open(opt_txt, 'wb') as f:
+                        f.write(before)
+                with open(os.path.join(os.path.dirname(opt_txt), 'video_opt.txt'), 'wt') as f:
+                    f.write(recorded.replace('\nbatchSize: 1\n', '\nbatchSize: %d\n' % opt.batchSize) if first.tile else recorded)
+            except OSError as e:
+                print('note: could not record the options (%s)' % e)
+        if opt.eval_noref and not opt.noref_csv:
+            opt.noref_csv = os.path.join(os.path.dirname(os.path.abspath(opt.video_out)), 'noref.csv')
+        return opt

@@ -1,0 +1,393 @@
+"""Dehaze a YUV4MPEG2 (.y4m) stream: reader, writer and the loop of dehaze_video.py.
+
+A y4m stream is one text line (`YUV4MPEG2 W.. H.. F.. I.. A.. C.. X..`) and then, per frame, a `FRAME` line and the planes Y, Cb, Cr as raw
+bytes -- what `ffmpeg -f yuv4mpegpipe`, x264, aomenc and vmaf read and write.  The frame bytes go to the device as they are; the colour
+conversion both ways runs there (ops.yuv_to_rgb_u8 / ops.rgb_to_yuv_u8, include/cfen_yuv.h) next to the forward.
+
+Threads: one reader fills pinned host buffers, one writer drains them; the main thread issues, per batch and on ONE stream, the copy in, the
+conversion, the forward, the conversion back and the copy out.  The ring holds --video_buffers slots; a slot goes reader -> main -> writer ->
+reader.  Everything on the device happens in frame order on that stream, so the output does not depend on timing or on the number of slots."""
+import os
+import queue
+import sys
+import threading
+import time
+
+from . import yuv
+
+MAX_HEADER = 8192
+ACCEPTED_C = ("420jpeg", "420mpeg2", "422", "444", "mono")
+
+
+class Y4MError(ValueError):
+    pass
+
+
+def _open(target, mode):
+    """(binary file object, do we close it): a path, '-' for stdin / stdout, or an open binary file object"""
+    if hasattr(target, "read") or hasattr(target, "write"):
+        return target, False
+    if target == "-":
+        return (sys.stdin.buffer if mode == "rb" else sys.stdout.buffer), False
+    return open(target, mode), True
+
+
+def parse_header(line):
+    """the fields of a `YUV4MPEG2 ...` line (bytes, with or without its newline) as a dict: width, height, chroma (one of ACCEPTED_C),
+    color_range ('full' | 'limited' | None), tags (every token after the magic).  Y4MError names the tag this project does not read."""
+    text = line.rstrip(b"\n").decode("ascii", "replace")
+    tokens = text.split(" ")
+    if tokens[0] != "YUV4MPEG2":
+        raise Y4MError("not a YUV4MPEG2 stream: the first line starts with %r" % text[:16])
+    tags = [t for t in tokens[1:] if t]
+    info = {"width": None, "height": None, "chroma": "420jpeg", "color_range": None, "tags": tags}
+    for t in tags:
+        key, value = t[0], t[1:]
+        if key in "WH":
+            if not value.isdigit() or not 1 <= int(value) <= yuv.MAX_EDGE:
+                raise Y4MError("y4m header: bad size tag %r (1 .. %d)" % (t, yuv.MAX_EDGE))
+            info["width" if key == "W" else "height"] = int(value)
+        elif key == "I":
+            if value not in ("p", "?"):
+                raise Y4MError("y4m header: interlaced stream (tag %r): only progressive frames (Ip) are dehazed" % t)
+        elif key == "C":
+            if value == "420":
+                value = "420jpeg"                      # mjpegtools: a plain 420 is 420jpeg
+            if value not in ACCEPTED_C:
+                why = "high bit depth" if "p1" in value or value.endswith("p9") else ("PAL-DV chroma siting" if value == "420paldv" else "unknown chroma format")
+                raise Y4MError("y4m header: tag %r (%s) is not supported: 8-bit %s only" % (t, why, ", ".join("C" + c for c in ACCEPTED_C)))
+            info["chroma"] = value
+        elif t.startswith("XCOLORRANGE="):
+            r = t.split("=", 1)[1].upper()
+            if r not in ("FULL", "LIMITED"):
+                raise Y4MError("y4m header: tag %r: XCOLORRANGE is FULL or LIMITED" % t)
+            info["color_range"] = r.lower()
+    if info["width"] is None or info["height"] is None:
+        raise Y4MError("y4m header: no %s tag in %r" % ("W" if info["width"] is None else "H", text))
+    return info
+
+
+def _check_frame_line(line, index):
+    """`line`: what readline gave where frame `index` starts (not empty)"""
+    if line == b"FRAME\n" or (line.startswith(b"FRAME ") and line.endswith(b"\n")):
+        return
+    if not line.endswith(b"\n") and (b"FRAME\n".startswith(line) or line.startswith(b"FRAME ")) and len(line) < MAX_HEADER:
+        raise Y4MError("y4m frame %d is cut short: the stream ends inside its FRAME line" % index)
+    raise Y4MError("y4m frame %d: expected a FRAME line, got %r" % (index, line[:16]))
+
+
+class Y4MReader:
+    """frames of a y4m stream, one at a time.  source: a path, '-' (stdin, binary) or a binary file object.  Reads that come back short (a pipe)
+    are continued.  `header` is the first line byte for byte, with its newline."""
+
+    def __init__(self, source):
+        self._f, self._own = _open(source, "rb")
+        line = self._f.readline(MAX_HEADER)
+        if not line.endswith(b"\n"):
+            raise Y4MError("y4m header: no end of line within %d bytes" % MAX_HEADER if len(line) >= MAX_HEADER else "y4m header: the stream ends inside it")
+        self.header = line
+        info = parse_header(line)
+        self.width, self.height, self.chroma, self.color_range, self.tags = (info[k] for k in ("width", "height", "chroma", "color_range", "tags"))
+        self.frame_bytes = yuv.frame_bytes(self.height, self.width, self.chroma)
+        self.frames_read = 0
+
+    def _fill(self, view):
+        """read len(view) bytes; returns how many arrived before the end of the stream"""
+        got, n = 0, len(view)
+        while got < n:
+            k = self._f.readinto(view[got:])
+            if not k:
+                break
+            got += k
+        return got
+
+    def read_frame_into(self, buf):
+        """the next frame's payload into `buf` (a writable buffer of frame_bytes bytes); False at the end of the stream.  Y4MError naming the
+        frame index when the stream ends inside a frame or a FRAME line is missing."""
+        line = self._f.readline(MAX_HEADER)
+        if not line:
+            return False
+        _check_frame_line(line, self.frames_read)
+        view = memoryview(buf).cast("B")
+        if len(view) != self.frame_bytes:
+            raise ValueError("read_frame_into needs a buffer of %d bytes, got %d" % (self.frame_bytes, len(view)))
+        got = self._fill(view)
+        if got != self.frame_bytes:
+            raise Y4MError("y4m frame %d is cut short: %d of %d bytes" % (self.frames_read, got, self.frame_bytes))
+        self.frames_read += 1
+        return True
+
+    def read_frame(self):
+        buf = bytearray(self.frame_bytes)
+        return bytes(buf) if self.read_frame_into(buf) else None
+
+    def check_whole_file(self):
+        """for a seekable source: walk every FRAME line without reading the payloads and return the number of frames, so that a stream cut short
+        is refused before any work is done; None for a pipe (there the cut shows when it is reached).  The position is restored."""
+        try:
+            if not self._f.seekable():
+                return None
+            start = self._f.tell()
+        except (OSError, ValueError, AttributeError):
+            return None
+        end = self._f.seek(0, os.SEEK_END)
+        self._f.seek(start)
+        n, pos = 0, start
+        try:
+            while pos < end:
+                line = self._f.readline(MAX_HEADER)
+                _check_frame_line(line, n)
+                pos += len(line) + self.frame_bytes
+                if pos > end:
+                    raise Y4MError("y4m frame %d is cut short: %d of %d bytes" % (n, self.frame_bytes - (pos - end), self.frame_bytes))
+                self._f.seek(pos)
+                n += 1
+        finally:
+            self._f.seek(start)
+        return n
+
+    def close(self):
+        if self._own:
+            self._f.close()
+
+
+class Y4MWriter:
+    """writes `header` (the input's first line, byte for byte) when the first frame arrives or at close(), then `FRAME\\n` + payload per frame"""
+
+    def __init__(self, target, header):
+        if not header.endswith(b"\n"):
+            raise ValueError("a y4m header ends with a newline")
+        self._target, self._header = target, header
+        self._f, self._own = None, False
+        self.frames_written = 0
+
+    def _start(self):
+        if self._f is None:
+            self._f, self._own = _open(self._target, "wb")
+            self._f.write(self._header)
+
+    def write_frame(self, payload):
+        self._start()
+        self._f.write(b"FRAME\n")
+        self._f.write(payload)
+        self.frames_written += 1
+
+    def close(self):
+        self._start()
+        self._f.flush()
+        if self._own:
+            self._f.close()
+
+
+def pick_matrix(choice, height):
+    return ("bt709" if height >= 720 else "bt601") if choice == "auto" else choice
+
+
+def pick_range(choice, color_range):
+    return (color_range or "limited") if choice == "auto" else choice
+
+
+class Slot:
+    """one slot of the ring: `rows_in` and `rows_out` are writable (batch, frame_bytes) uint8 arrays (pinned host memory in run()); the reader sets
+    `n` (frames held) and `first` (index of the first one), process() may hang anything else on `extra`"""
+    __slots__ = ("rows_in", "rows_out", "n", "first", "done", "extra")
+
+    def __init__(self, rows_in, rows_out, extra=None):
+        self.rows_in, self.rows_out, self.extra = rows_in, rows_out, extra
+        self.n = self.first = 0
+        self.done = None
+
+
+def pump(reader, writer, batch, slots, process, seconds=None):
+    """Move every frame of `reader` through `process` into `writer`, `batch` frames at a time, and return the number of frames.
+
+    One reader thread fills slots, the calling thread hands each filled slot to process(slot) -- which arranges for slot.rows_out[:slot.n] to hold
+    the output and returns None or an object whose synchronize() waits for that -- and one writer thread waits and writes.  A slot goes
+    reader -> caller -> writer -> reader, so at most len(slots) batches are in the ring and the output is in frame order whatever the timing.
+    Failures end the run, never hang it:
+      the writer's (a closed pipe, a full disk): the writer keeps handing slots back so that nobody blocks on the ring, wakes the caller, and its
+        exception is raised as soon as the caller has returned from the process() it is in;
+      the reader's (a stream cut short): every whole frame read before it -- the batches already queued and the part of the batch it happened
+        in -- is still processed and written, then its exception is raised;
+      process()'s own: raised once the writer has written what was already handed over."""
+    free, filled, towrite = queue.Queue(), queue.Queue(), queue.Queue()
+    for s in slots:
+        free.put(s)
+    read_failure, write_failure = [], []
+    seconds = seconds if seconds is not None else {}
+    seconds.setdefault("wait_for_frames", 0.0)
+    seconds.setdefault("issue", 0.0)
+
+    def read_loop():
+        index = 0
+        while True:
+            s = free.get()
+            if s is None:
+                return
+            n = 0
+            try:
+                while n < batch and reader.read_frame_into(s.rows_in[n]):
+                    n += 1
+            except BaseException as e:
+                read_failure.append(e)
+            s.n, s.first = n, index
+            index += n
+            if n:
+                filled.put(s)
+            if n < batch or read_failure:
+                filled.put(None)
+                return
+
+    def write_loop():
+        while True:
+            s = towrite.get()
+            if s is None:
+                return
+            if not write_failure:
+                try:
+                    if s.done is not None:
+                        s.done.synchronize()
+                    for k in range(s.n):
+                        writer.write_frame(s.rows_out[k])
+                except BaseException as e:
+                    write_failure.append(e)
+                    filled.put(None)          # wakes the caller if it is waiting for frames
+            free.put(s)                       # also after a failure: the ring keeps turning until the caller has seen it
+
+    threads = [threading.Thread(target=read_loop, name="y4m-reader", daemon=True), threading.Thread(target=write_loop, name="y4m-writer", daemon=True)]
+    for t in threads:
+        t.start()
+    frames = 0
+    try:
+        while True:
+            t0 = time.perf_counter()
+            s = filled.get()
+            seconds["wait_for_frames"] += time.perf_counter() - t0
+            if s is None or write_failure:
+                break
+            t0 = time.perf_counter()
+            s.done = process(s)
+            towrite.put(s)
+            frames += s.n
+            seconds["issue"] += time.perf_counter() - t0
+    finally:
+        towrite.put(None)
+        free.put(None)
+        threads[1].join()
+    if write_failure:
+        raise write_failure[0]
+    writer.close()
+    if read_failure:
+        raise read_failure[0]
+    return frames
+
+
+class UnsafeHalfFrames(Y4MError):
+    """--precision half: a guard check failed after fp16 frames had already left in the stream"""
+
+
+def run(opt, log=print):
+    """the loop of dehaze_video.py.  opt: VideoOptions().parse().  Returns the number of frames.  Everything printed goes through `log` (stderr when
+    the video leaves on stdout)."""
+    import torch
+    from . import metrics, ops
+    from .models import create_model
+
+    reader = Y4MReader(opt.video_in)
+    H, W, chroma = reader.height, reader.width, reader.chroma
+    matrix = pick_matrix(opt.video_matrix, H)
+    full = pick_range(opt.video_range, reader.color_range) == "full"
+    log("video: %d x %d C%s, matrix %s (%s), range %s (%s)" % (W, H, chroma, matrix, "auto: H >= 720 is bt709" if opt.video_matrix == "auto" else "given",
+                                                               "full" if full else "limited",
+                                                               ("auto: XCOLORRANGE" if reader.color_range else "auto: no XCOLORRANGE tag") if opt.video_range == "auto" else "given"))
+    from .config import VARIANTS, FULL_RES_VARIANTS
+    T = opt.loadSize if VARIANTS.get(opt.model_G, "v3") in FULL_RES_VARIANTS else 2 * opt.loadSize      # the generator's image edge (as in test.py)
+    route = "plain" if (H, W) == (T, T) else ("fit" if opt.fit else ("tile" if opt.tile else None))
+    if route is None:
+        raise Y4MError("the frames are %d x %d but the generator takes %d x %d: give --fit (one resampled forward per frame) or --tile "
+                       "(overlapping tiles)" % (W, H, T, T))
+    n_known = reader.check_whole_file()       # a file cut short is refused here, before any forward
+    model = create_model(opt)
+    model.setup(opt)
+    model.set_noref_scoring(False)            # the frames are scored here (all three routes), not in model.test()
+    net = model.netG
+    if net.cfg.image_size != T:
+        raise RuntimeError("the generator's image size is %d, expected %d" % (net.cfg.image_size, T))
+    if route == "plain":
+        model.use_native_size_route()         # frames of the generator's own size: the plain --u8_input route whatever was asked for other sizes
+    nb, B = reader.frame_bytes, opt.batchSize
+    dev = model.device
+    stream = torch.cuda.current_stream()
+    writer = Y4MWriter(opt.video_out, reader.header)
+    slots = []
+    for _ in range(opt.video_buffers):
+        pins = (torch.empty(B, nb, dtype=torch.uint8).pin_memory(), torch.empty(B, nb, dtype=torch.uint8).pin_memory())
+        slots.append(Slot(pins[0].numpy(), pins[1].numpy(), extra=pins))
+    d_in = torch.empty(B, nb, dtype=torch.uint8, device=dev)
+    d_out = torch.empty(B, nb, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+    noref_rows = []
+    seconds = {"wait_for_frames": 0.0, "issue": 0.0, "noref": 0.0}
+    actnorm = {"ready": False}                # asked of the device until it is true, then remembered (the layers never go back)
+
+    def through_model(x, first):
+        """the model's own batch route, the one test.py takes (the half guard included where test.py applies it)"""
+        model.set_input({"B": x, "B_paths": ["frame_%06d" % (first + k) for k in range(x.shape[0])]})
+        model.test(opt)
+        return model.output_bytes()
+
+    def process(s):
+        n = s.n
+        pin_in, pin_out = s.extra
+        d_in[:n].copy_(pin_in[:n], non_blocking=True)
+        x = ops.yuv_to_rgb_u8(d_in[:n], H, W, chroma, matrix, full, out=rgb[:n])
+        if route != "tile":
+            y = through_model(x, s.first)
+        else:
+            parts, lo = [], 0
+            if not actnorm["ready"]:
+                actnorm["ready"] = model.actnorm_ready()
+            if not actnorm["ready"]:
+                # the very first frame of a checkpoint whose ActNorm layers are uninitialised runs alone through the model's route, which
+                # initialises them from it as test.py --tile does with its first image
+                parts.append(through_model(x[:1], s.first))
+                actnorm["ready"] = model.actnorm_ready()
+                lo = 1
+            if lo < n:
+                with torch.no_grad():
+                    outs = net.forward_tiled_many([x[k] for k in range(lo, n)], overlap=opt.tile_overlap, tile_batch=opt.tile_batch, output_u8=True,
+                                                  self_ensemble=bool(getattr(opt, "self_ensemble", False)))
+                parts.append(torch.stack([o[2] for o in outs]))
+            y = parts[0] if len(parts) == 1 else torch.cat(parts)
+        y = y.contiguous()
+        if opt.eval_noref:
+            t1 = time.perf_counter()
+            for k, row in enumerate(metrics.noref(x, y, opt.noref_radius)):
+                noref_rows.append(("frame_%06d" % (s.first + k),) + tuple(row))
+            seconds["noref"] += time.perf_counter() - t1
+        ops.rgb_to_yuv_u8(y, chroma, matrix, full, out=d_out[:n])
+        pin_out[:n].copy_(d_out[:n], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(stream)
+        return done
+
+    t_start = time.perf_counter()
+    frames = pump(reader, writer, B, slots, process, seconds)
+    reader.close()
+    total = time.perf_counter() - t_start
+    if n_known is not None and n_known != frames:
+        raise Y4MError("read %d frames of the %d the file holds" % (frames, n_known))
+    model.finish_half_guard()
+    if opt.eval_noref:
+        with open(opt.noref_csv, "w") as f:
+            f.write(metrics.format_noref_csv(noref_rows))
+        log(metrics.noref_summary_line(noref_rows))
+        log("noref: wrote %s" % opt.noref_csv)
+    log("video: route %s, %d frames per batch, %d buffers; main-thread seconds %s" % (route, B, opt.video_buffers, {k: round(v, 3) for k, v in seconds.items()}))
+    log("video: %d frames in %.2f s = %.1f frames/s stream to stream" % (frames, total, frames / max(total, 1e-9)))
+    if model.redo_paths:
+        # test.py runs such images again in fp32 and rewrites their files; a stream has already left.  The run must not look like a success.
+        raise UnsafeHalfFrames("a --precision half check failed after %d frames (%s .. %s) had been written from fp16 forwards that are now known "
+                               "to be unsafe; a stream cannot be rewritten: the output is not to be used, run again with --precision single"
+                               % (len(model.redo_paths), model.redo_paths[0], model.redo_paths[-1]))
+    return frames
