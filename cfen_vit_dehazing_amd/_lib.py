@@ -175,6 +175,12 @@ YUV_SIGNATURES = {
     "cfen_rgb_to_yuv_u8": (_I, [_P, _I, _I, _I, _I, YuvTableC, _P, c_size_t, _P]),
 }
 
+# every symbol include/cfen_temporal.h declares: the temporal stabilisation extension, bound beside the other six
+TEMPORAL_SIGNATURES = {
+    "cfen_temporal_blend": (_I, [_P, _P, _P, _I, _I, _I, _I, c_float, c_float, _I, _P, _P, _P]),
+    "cfen_temporal_apply_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+}
+
 _lib = None
 
 
@@ -188,7 +194,7 @@ def load():
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()) + \
-            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()) + list(YUV_SIGNATURES.items()):
+            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()) + list(YUV_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -569,6 +569,70 @@ def guided_upsample_u8(guide_hi, guide_lo, src_lo, radius=2, eps=1e-4, out=None)
     return guided_apply_u8(guided_coef_u8(guide_lo, src_lo, radius, eps), guide_hi, out=out)
 
 
+def _temporal_params(what, radius, motion, strength):
+    import math
+    try:
+        r, m, s = int(radius), float(motion), float(strength)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: radius must be an integer in 1 .. 16, motion and strength numbers, got radius %r, motion %r, strength %r"
+                         % (what, radius, motion, strength))
+    if r != radius or not 1 <= r <= 16:
+        raise ValueError("%s: radius must be an integer in 1 .. 16, got %r" % (what, radius))
+    if not (math.isfinite(m) and m > 0):
+        raise ValueError("%s: motion must be finite and > 0, got %r" % (what, motion))
+    if not 0 <= s < 1:
+        raise ValueError("%s: strength must be in [0, 1), got %r" % (what, strength))
+    return r, m, s
+
+
+def temporal_blend(guide, prev_guide, coef, state, radius=2, motion=8.0, strength=0.8, have_state=True, out=None):
+    """cfen_temporal_blend (include/cfen_temporal.h): the motion-gated recursion S_t = c_t + k (S_{t-1} - c_t) on the coefficient fields coef
+    (B,h,w,6) float32 of the B consecutive working-resolution frames guide (B,h,w,3) uint8, in one launch: returns delta (B,h,w,6) float32 =
+    S_t - c_t and updates state (h,w,6) float32 in place to S of the last frame.  prev_guide (h,w,3) uint8 is the frame before guide[0]; it is only
+    read.  have_state False: guide[0] is the first frame of a stream, prev_guide (may be None) and what state holds are not looked at.  out: the
+    caller's (B,h,w,6) float32 tensor."""
+    _guided_images("temporal_blend", guide=guide)
+    B, h, w, _ = guide.shape
+    dev = guide.device
+    if not isinstance(coef, torch.Tensor) or tuple(coef.shape) != (B, h, w, 6) or coef.dtype != torch.float32 or coef.device != dev:
+        raise ValueError("temporal_blend needs coef as a contiguous (%d,%d,%d,6) float32 tensor on the device of guide, got %s"
+                         % (B, h, w, "%s %s" % (tuple(coef.shape), coef.dtype) if isinstance(coef, torch.Tensor) else type(coef).__name__))
+    if not isinstance(state, torch.Tensor) or tuple(state.shape) != (h, w, 6) or state.dtype != torch.float32 or state.device != dev:
+        raise ValueError("temporal_blend needs state as a contiguous (%d,%d,6) float32 tensor on the device of guide, got %s"
+                         % (h, w, "%s %s" % (tuple(state.shape), state.dtype) if isinstance(state, torch.Tensor) else type(state).__name__))
+    have_state = bool(have_state)
+    if have_state and (not isinstance(prev_guide, torch.Tensor) or tuple(prev_guide.shape) != (h, w, 3) or prev_guide.dtype != torch.uint8 or
+                       prev_guide.device != dev):
+        raise ValueError("temporal_blend with have_state needs prev_guide as a contiguous (%d,%d,3) uint8 tensor on the device of guide, got %s"
+                         % (h, w, "%s %s" % (tuple(prev_guide.shape), prev_guide.dtype) if isinstance(prev_guide, torch.Tensor) else type(prev_guide).__name__))
+    _cuda(coef, state, prev_guide if have_state else None)
+    radius, motion, strength = _temporal_params("temporal_blend", radius, motion, strength)
+    out = _out(out, (B, h, w, 6), torch.float32, dev, "temporal_blend")
+    check(_lib.load().cfen_temporal_blend(ptr(guide), ptr(prev_guide if have_state else None), ptr(coef), B, h, w, radius, motion, strength,
+                                          int(have_state), ptr(state), ptr(out), current_stream()), "temporal_blend")
+    return out
+
+
+def temporal_apply_u8(delta, guide_hi, src_hi, out=None):
+    """cfen_temporal_apply_u8 (include/cfen_temporal.h): delta (B,h,w,6) float32 of temporal_blend, upsampled bilinearly as guided_apply_u8 upsamples
+    to the size of guide_hi and src_hi (B,H,W,3) uint8 -- the hazy and the dehazed frames -- and applied as a correction of src_hi:
+    (B,H,W,3) uint8 = clamp(floor(src_hi + DA * guide_hi + DB + 0.5), 0, 255).  out: the caller's (B,H,W,3) uint8 tensor, which may be a lane of a
+    larger slab (no alignment is assumed)."""
+    _guided_images("temporal_apply_u8", guide_hi=guide_hi, src_hi=src_hi)
+    if guide_hi.shape != src_hi.shape or guide_hi.device != src_hi.device:
+        raise ValueError("temporal_apply_u8: guide_hi %s and src_hi %s differ in shape or device" % (tuple(guide_hi.shape), tuple(src_hi.shape)))
+    if not isinstance(delta, torch.Tensor) or delta.dim() != 4 or delta.shape[3] != 6 or delta.dtype != torch.float32 or min(delta.shape) < 1 or \
+            delta.shape[0] != guide_hi.shape[0] or delta.device != guide_hi.device:
+        raise ValueError("temporal_apply_u8 needs delta as a contiguous (B,h,w,6) float32 tensor for the %d images of guide_hi, got %s"
+                         % (guide_hi.shape[0], "%s %s" % (tuple(delta.shape), delta.dtype) if isinstance(delta, torch.Tensor) else type(delta).__name__))
+    _cuda(delta)
+    B, H, W, _ = guide_hi.shape
+    out = _out(out, (B, H, W, 3), torch.uint8, guide_hi.device, "temporal_apply_u8")
+    check(_lib.load().cfen_temporal_apply_u8(ptr(delta), B, delta.shape[1], delta.shape[2], ptr(guide_hi), ptr(src_hi), H, W, ptr(out), current_stream()),
+          "temporal_apply_u8")
+    return out
+
+
 def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     """cfen_image_metrics: per image pair (sse, ssim) as two float64 CUDA tensors of shape (B,), in one fused pass.
 

@@ -22,10 +22,50 @@ class VideoOptions(TestOptions):
                        help='sample range of the stream; auto: the XCOLORRANGE tag of the header, limited (16 .. 235) without one')
         p.add_argument('--video_buffers', type=int, default=4, help='slots of the ring of pinned host buffers between the reader, the device and the writer (each holds a batch both ways)')
         p.add_argument('--noref_csv', type=str, default=None, help='--eval_noref: where noref.csv goes (default: beside --out; required when --out is -)')
+        p.add_argument('--temporal', action='store_true',
+                       help='(extension) temporal stabilisation: smooth the local affine model out ~ a * hazy + b of neighbouring frames over time and '
+                            'correct each dehazed frame by the change of its coefficients (DESIGN section 18); the first frame passes unchanged')
+        p.add_argument('--temporal_strength', type=float, default=None,
+                       help='--temporal: weight of the past in the recursion, in [0, 1) (default 0.8); 0 leaves every frame as the generator wrote it')
+        p.add_argument('--temporal_motion', type=float, default=None,
+                       help='--temporal: mean absolute change of the hazy bytes over the window, in levels, at which the recursion is switched off '
+                            '(default 8.0), finite and > 0. The defaults of the --temporal options come from a synthetic scattering-model experiment '
+                            '(DESIGN section 18), not from a checkpoint')
+        p.add_argument('--temporal_radius', type=int, default=None, help='--temporal: radius of the (2 r + 1)^2 window at the working resolution, 1 .. 16 (default 2)')
+        p.add_argument('--temporal_eps', type=float, default=None,
+                       help='--temporal: regulariser of the local variance, in squared units of the [0, 1] intensity scale, finite and > 0 (default 1e-4)')
+        p.add_argument('--temporal_down', type=str, default=None,
+                       help='--temporal: integer factor >= 1 between the frame and the working resolution, or auto = ceil(max(H, W) / 1024) (default auto)')
         for a in p._actions:
             if a.dest == 'dataroot':
                 a.required = False
         p.set_defaults(batchSize=8, dataroot='')
+
+    TEMPORAL = ('strength', 'motion', 'radius', 'eps', 'down')
+
+    @staticmethod
+    def _without_temporal(text):
+        """a run without --temporal prints and records what it always did"""
+        return ''.join(l for l in text.splitlines(True) if not l.startswith('temporal'))
+
+    def _check_temporal(self, first):
+        """the refusals of the --temporal options; returns the defaults of those not given, as arguments"""
+        from .. import temporal
+        given = {k: getattr(first, 'temporal_' + k) for k in self.TEMPORAL if getattr(first, 'temporal_' + k) is not None}
+        if not first.temporal:
+            if given:
+                raise ValueError('%s only applies with --temporal' % ', '.join('--temporal_' + k for k in given))
+            return []
+        values = dict(temporal.DEFAULTS, **given)
+        if values['down'] != 'auto':
+            if not values['down'].isdigit() or int(values['down']) < 1:
+                raise ValueError("--temporal_down must be auto or an integer >= 1 (got --temporal_down %s)" % values['down'])
+            values['down'] = int(values['down'])
+        try:
+            temporal.check_params(values['radius'], values['eps'], values['strength'], values['motion'], values['down'], '--temporal')
+        except ValueError as e:
+            raise ValueError(str(e).replace('--temporal: ', '--temporal_', 1))
+        return [a for k in self.TEMPORAL if k not in given for a in ('--temporal_' + k, repr(temporal.DEFAULTS[k]) if k != 'down' else 'auto')]
 
     def parse(self, argv=None):
         import sys
@@ -43,6 +83,7 @@ class VideoOptions(TestOptions):
             raise ValueError('--eval_noref with --out -: say where noref.csv goes with --noref_csv PATH')
         if first.noref_csv and not first.eval_noref:
             raise ValueError('--noref_csv is where --eval_noref writes: it needs --eval_noref')
+        extra_temporal = self._check_temporal(first)
         # test.py's own checks run on what test.py would be given: frames in order, and --tile there means one image per call.  What that parse
         # prints and records is held back, corrected to the batch size this run really uses, and recorded in a file of its own: opt.txt stays
         # what the last test.py run of the same --name wrote
@@ -53,14 +94,18 @@ class VideoOptions(TestOptions):
         before = open(opt_txt, 'rb').read() if os.path.exists(opt_txt) else None
         held = io.StringIO()
         with contextlib.redirect_stdout(held):
-            opt = TestOptions.parse(self, argv + extra)
+            opt = TestOptions.parse(self, argv + extra + extra_temporal)
         opt.batchSize = first.batchSize
+        if opt.temporal and opt.temporal_down != 'auto':
+            opt.temporal_down = int(opt.temporal_down)
         text = held.getvalue().replace('\nbatchSize: 1\n', '\nbatchSize: %d\n' % opt.batchSize) if first.tile else held.getvalue()
+        text = text if first.temporal else self._without_temporal(text)
         sys.stdout.write(text)
         sys.stdout.flush()
         if opt.dist_rank == 0:
             try:
                 recorded = open(opt_txt).read()
+                recorded = recorded if first.temporal else self._without_temporal(recorded)
                 if before is None:
                     os.remove(opt_txt)
                 else:

@@ -1,0 +1,93 @@
+"""Temporal stabilisation of a dehazed stream (include/cfen_temporal.h states the definition).
+
+The generator dehazes every frame on its own, and a small change of the input changes its estimate of airlight and transmission: the output
+shimmers.  A Stabiliser fits, per frame, the local affine model out ~ a * hazy + b of guided upsampling (ops.guided_coef_u8) at a working
+resolution, smooths (a, b) over time by a recursion that a motion test switches off where the scene changed (ops.temporal_blend), and corrects
+the full-resolution output by the CHANGE of the coefficients (ops.temporal_apply_u8): the network's own detail stays, and where nothing is
+smoothed the bytes are the network's.  Everything runs on the current stream; nothing synchronises with the host."""
+import math
+
+import torch
+
+from . import ops
+
+DEFAULTS = {"radius": 2, "eps": 1e-4, "strength": 0.8, "motion": 8.0, "down": "auto"}
+
+
+def check_params(radius, eps, strength, motion, down, what="Stabiliser"):
+    """(radius, eps, strength, motion, down) as int, float, float, float, int or 'auto'; ValueError naming the argument out of range"""
+    try:
+        r, e, s, m = int(radius), float(eps), float(strength), float(motion)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: radius must be an integer, eps, strength and motion numbers, got %r, %r, %r, %r" % (what, radius, eps, strength, motion))
+    if r != radius or not 1 <= r <= 16:
+        raise ValueError("%s: radius must be an integer in 1 .. 16, got %r" % (what, radius))
+    if not (math.isfinite(e) and e > 0):
+        raise ValueError("%s: eps must be finite and > 0, got %r" % (what, eps))
+    if not 0 <= s < 1:
+        raise ValueError("%s: strength must be in [0, 1), got %r" % (what, strength))
+    if not (math.isfinite(m) and m > 0):
+        raise ValueError("%s: motion must be finite and > 0, got %r" % (what, motion))
+    if down != "auto":
+        try:
+            d = int(down)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("%s: down must be 'auto' or an integer >= 1, got %r" % (what, down))
+        if d != down or d < 1:
+            raise ValueError("%s: down must be 'auto' or an integer >= 1, got %r" % (what, down))
+        down = d
+    return r, e, s, m, down
+
+
+def working_size(H, W, down="auto"):
+    """(S, h, w): the factor and the working resolution of H x W frames; auto is S = ceil(max(H, W) / 1024)"""
+    S = -(-max(H, W) // 1024) if down == "auto" else int(down)
+    return S, -(-H // S), -(-W // S)
+
+
+class Stabiliser:
+    """step(hazy_u8, out_u8) for consecutive batches of consecutive frames, (n,H,W,3) uint8 CUDA tensors: the stabilised (n,H,W,3) uint8 frames.
+    The first frame after construction or reset() passes unchanged.  The object owns the recursion's state, a copy of the last working-resolution
+    hazy frame and its scratch tensors; the result does not depend on how the frames are grouped into batches."""
+
+    def __init__(self, radius=2, eps=1e-4, strength=0.8, motion=8.0, down="auto"):
+        self.radius, self.eps, self.strength, self.motion, self.down = check_params(radius, eps, strength, motion, down)
+        self.reset()
+
+    def reset(self):
+        """the next frame is the first of a stream (frames of another size may follow)"""
+        self._have = False
+        self._key = None
+        self._state = self._prev = self._coef = self._delta = None
+
+    def step(self, hazy_u8, out_u8, out=None):
+        for name, t in (("hazy_u8", hazy_u8), ("out_u8", out_u8)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8 or min(t.shape) < 1 or not t.is_cuda or \
+                    not t.is_contiguous():
+                raise ValueError("Stabiliser.step needs %s as a contiguous (n,H,W,3) uint8 CUDA tensor, got %s"
+                                 % (name, "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if hazy_u8.shape != out_u8.shape or hazy_u8.device != out_u8.device:
+            raise ValueError("Stabiliser.step: hazy_u8 %s and out_u8 %s differ in shape or device" % (tuple(hazy_u8.shape), tuple(out_u8.shape)))
+        n, H, W, _ = hazy_u8.shape
+        dev = hazy_u8.device
+        key = (H, W, dev)
+        if self._key is not None and key != self._key:
+            raise ValueError("Stabiliser.step: frames of %d x %d on %s after frames of %d x %d on %s: reset() starts a new stream"
+                             % (H, W, dev, self._key[0], self._key[1], self._key[2]))
+        S, h, w = working_size(H, W, self.down)
+        if self._key is None:
+            self._key = key
+            self._state = torch.empty(h, w, 6, dtype=torch.float32, device=dev)
+            self._prev = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
+        if self._coef is None or self._coef.shape[0] < n:
+            self._coef = torch.empty(n, h, w, 6, dtype=torch.float32, device=dev)
+            self._delta = torch.empty(n, h, w, 6, dtype=torch.float32, device=dev)
+        if S == 1:
+            I, P = hazy_u8, out_u8
+        else:
+            I, P = ops.resample_u8(hazy_u8, (h, w), filter="box"), ops.resample_u8(out_u8, (h, w), filter="box")
+        coef = ops.guided_coef_u8(I, P, self.radius, self.eps, out=self._coef[:n])
+        delta = ops.temporal_blend(I, self._prev, coef, self._state, self.radius, self.motion, self.strength, self._have, out=self._delta[:n])
+        self._prev.copy_(I[n - 1])                 # after the launch that read it, on the same stream
+        self._have = True
+        return ops.temporal_apply_u8(delta, hazy_u8, out_u8, out=out)

@@ -329,6 +329,13 @@ def run(opt, log=print):
     noref_rows = []
     seconds = {"wait_for_frames": 0.0, "issue": 0.0, "noref": 0.0}
     actnorm = {"ready": False}                # asked of the device until it is true, then remembered (the layers never go back)
+    stabiliser = None
+    if getattr(opt, "temporal", False):
+        from . import temporal
+        stabiliser = temporal.Stabiliser(opt.temporal_radius, opt.temporal_eps, opt.temporal_strength, opt.temporal_motion, opt.temporal_down)
+        S, h, w = temporal.working_size(H, W, stabiliser.down)
+        log("video: temporal stabilisation at %d x %d (1/%d), radius %d, eps %g, strength %g, motion %g levels"
+            % (w, h, S, stabiliser.radius, stabiliser.eps, stabiliser.strength, stabiliser.motion))
 
     def through_model(x, first):
         """the model's own batch route, the one test.py takes (the half guard included where test.py applies it)"""
@@ -360,6 +367,8 @@ def run(opt, log=print):
                 parts.append(torch.stack([o[2] for o in outs]))
             y = parts[0] if len(parts) == 1 else torch.cat(parts)
         y = y.contiguous()
+        if stabiliser is not None:
+            y = stabiliser.step(x, y)         # all three routes; --eval_noref scores, and the stream carries, the stabilised bytes
         if opt.eval_noref:
             t1 = time.perf_counter()
             for k, row in enumerate(metrics.noref(x, y, opt.noref_radius)):
