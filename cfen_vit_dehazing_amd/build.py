@@ -81,13 +81,8 @@ def build(force=False, verbose=False, packed_fp32=False, lib=None, objdir=None):
     objdir = objdir or os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_hip.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_resample.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_guided.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_colordiff.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_noref.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_yuv.h"))
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "cfen_temporal.h"))
+    include = os.path.join(os.path.dirname(HERE), "include")
+    headers += [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h")]
     headers.append(os.path.abspath(__file__))          # flags live here
     objs = []
     procs = []

@@ -255,4 +255,15 @@ static inline bool cfen_first_use_on_device(bool (&flags)[64]) {
   return first;
 }
 
-static inline bool cfen_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool cfen_aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }      // n: a power of two
+static inline bool cfen_aligned16(const void* p) { return cfen_aligned(p, 16); }
+
+// no two of the n byte ranges overlap (a null pointer is a range that is not there)
+static inline bool cfen_ranges_disjoint(const void* const* p, const long long* bytes, int n) {
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(p[i]), b = reinterpret_cast<uintptr_t>(p[j]);
+      if (p[i] && p[j] && a < b + (uintptr_t)bytes[j] && b < a + (uintptr_t)bytes[i]) return false;
+    }
+  return true;
+}

@@ -8,13 +8,12 @@
 //                        values are added in pixel order in fp64, the wave's 64 sums by a shuffle butterfly, the four waves' sums through LDS
 //                        in wave order; thread 0 writes the workgroup's one partial.  The map, when asked for, is stored as 16 bytes where
 //                        the image's map begins on a 16-byte boundary, as single floats elsewhere and in the tail.
-//   k_ciede2000_finish : one workgroup per image adds the partials in the fixed order of k_image_metrics_finish (thread t takes partials
-//                        t, t + 256, ..., then a fixed LDS tree) and divides by H W.
+//   k_ciede2000_finish : one workgroup per image adds the partials in the fixed order of img_reduce_partials (cfen_image.hpp) and divides by H W.
 // Two launches; no atomics, no counters, no scratch memory (private segment 0: checked with -Rpass-analysis=kernel-resource-usage).
 #include <math.h>
 
 #include "../../include/cfen_colordiff.h"
-#include "cfen_common.hpp"
+#include "cfen_image.hpp"
 
 namespace {
 
@@ -101,12 +100,6 @@ CFEN_DEV float cd_de00(const Lab p, const Lab q) {
   return sqrtf(fmaxf(tl * tl + tc * tc + th * th + Rt * tc * th, 0.f));
 }
 
-CFEN_DEV double cd_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);      // butterfly: every lane ends with the bitwise identical total
-  return v;
-}
-
 union CdBytes {
   unsigned u[3];
   unsigned char c[12];
@@ -167,25 +160,17 @@ __global__ __launch_bounds__(256) void k_ciede2000(const unsigned char* __restri
         if (k < n) m[k] = de[k];
     }
   }
-  s = cd_wave_sum(s);
+  s = wave_sum(s);
   if ((tid & 63) == 0) red[tid >> 6] = s;
   __syncthreads();
-  if (tid == 0) part[(long long)img * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  if (tid == 0) part[(long long)img * gridDim.x + blockIdx.x] = block4_sum(red, 1);
 }
 
 __global__ __launch_bounds__(256) void k_ciede2000_finish(const double* __restrict__ part, int nparts, double count, double* __restrict__ out) {
-  __shared__ double red[256];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const double* p = part + (long long)b * nparts;
-  double s = 0.0;
-  for (int i = tid; i < nparts; i += 256) s += p[i];
-  red[tid] = s;
-  __syncthreads();
-  for (int n = 128; n >= 1; n >>= 1) {
-    if (tid < n) red[tid] += red[tid + n];
-    __syncthreads();
-  }
-  if (tid == 0) out[b] = red[0] / count;
+  __shared__ double red[1][256];
+  const int b = blockIdx.x;
+  img_reduce_partials<1>(part + (long long)b * nparts, nparts, red);
+  if (threadIdx.x == 0) out[b] = red[0][0] / count;
 }
 
 bool cd_dims_ok(int B, int H, int W) { return B >= 1 && B <= CD_MAX_BATCH && H >= 1 && W >= 1 && H <= CD_MAX_EDGE && W <= CD_MAX_EDGE; }
@@ -204,10 +189,8 @@ extern "C" int cfen_ciede2000_u8(const unsigned char* a, const unsigned char* b,
   CFEN_CHECK_ARG(a && b && table && scratch && out, "ciede2000_u8: null pointer (a, b, table, scratch and out are all required)");
   CFEN_CHECK_ARG(B >= 1 && B <= CD_MAX_BATCH, "ciede2000_u8: B = %d outside 1 .. %d", B, CD_MAX_BATCH);
   CFEN_CHECK_ARG(H >= 1 && W >= 1 && H <= CD_MAX_EDGE && W <= CD_MAX_EDGE, "ciede2000_u8: sizes H = %d, W = %d outside 1 .. %d", H, W, CD_MAX_EDGE);
-  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 7) == 0 && (reinterpret_cast<uintptr_t>(scratch) & 7) == 0,
-                 "ciede2000_u8: out and scratch must be 8-byte aligned (doubles)");
-  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(table) & 3) == 0 && (reinterpret_cast<uintptr_t>(map) & 3) == 0,
-                 "ciede2000_u8: table and map must be 4-byte aligned (floats)");
+  CFEN_CHECK_ARG(cfen_aligned(out, 8) && cfen_aligned(scratch, 8), "ciede2000_u8: out and scratch must be 8-byte aligned (doubles)");
+  CFEN_CHECK_ARG(cfen_aligned(table, 4) && cfen_aligned(map, 4), "ciede2000_u8: table and map must be 4-byte aligned (floats)");
   const long long npix = (long long)H * W;
   const int nparts = (int)cd_parts(H, W);
   hipStream_t s = (hipStream_t)stream;

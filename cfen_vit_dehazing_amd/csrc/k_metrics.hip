@@ -15,8 +15,8 @@
 //                          and forms 6 SSIM map values.
 //                     Per-thread sums are fp64 (the squared error of uint8 input is summed in integers first: exact), reduced over the wave with
 //                     shuffles, over the 4 waves through LDS in wave order, and written as this tile's (sse, ssim sum) pair to `part`.
-//   k_image_metrics_finish : one workgroup per image adds the tiles' pairs in a fixed order in fp64 (thread t takes tiles t, t + 256, ... in
-//                     increasing order, then a fixed LDS tree) and writes out[b] = (sse, ssim sum / count).
+//   k_image_metrics_finish : one workgroup per image adds the tiles' pairs in the fixed order of img_reduce_partials (cfen_image.hpp) and writes
+//                     out[b] = (sse, ssim sum / count).
 // No atomics and no counters: the same inputs give the same bits on every run, on any stream, at any batch size.
 //
 // MS-SSIM (cfen_image_msssim) runs the same tile body once per pyramid level, five launches and one finish:
@@ -27,7 +27,7 @@
 //                     own.  Level 0 reads the caller's images (and sums the squared error as above), levels 1 .. 4 read the workspace.
 //   k_msssim_finish : one workgroup per (level, image) adds that level's per-tile (sse, ssim sum, cs sum) in the order of k_image_metrics_finish.
 // Level 0 runs the very instructions of k_image_metrics on the same tiles, so its (sse, ssim) come out bit for bit the same.
-#include "cfen_common.hpp"
+#include "cfen_image.hpp"
 
 namespace {
 
@@ -43,12 +43,6 @@ struct MetricsGeom {
   int C, H, W, nty, ntx;
   float lo, range;      // fp32 input: v -> (v - lo) / range
 };
-
-CFEN_DEV double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);      // butterfly: every lane ends with the bitwise identical total
-  return v;
-}
 
 // one SSIM map value from the five filtered quantities.  No FMA contraction: with a == b the numerator and the denominator must come out
 // bitwise equal (2 m m against m m + m m), so that identical images score exactly 1
@@ -204,7 +198,7 @@ CFEN_DEV void metrics_tile(const void* __restrict__ pa, const void* __restrict__
     if (MS) red[wave][NP - 1] = cs;
   }
   __syncthreads();
-  if (tid < NP) part[((long long)b * g.nty * g.ntx + tile) * NP + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  if (tid < NP) part[((long long)b * g.nty * g.ntx + tile) * NP + tid] = block4_sum(&red[0][tid], NP);
 }
 
 template <bool U8>
@@ -221,24 +215,9 @@ __global__ __launch_bounds__(256) void k_msssim_level(const void* __restrict__ p
 
 __global__ __launch_bounds__(256) void k_image_metrics_finish(const double* __restrict__ part, int ntiles, double count, double* __restrict__ out) {
   __shared__ double red[2][256];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const double* p = part + (long long)b * ntiles * 2;
-  double s0 = 0.0, s1 = 0.0;
-  for (int i = tid; i < ntiles; i += 256) {
-    s0 += p[2 * i];
-    s1 += p[2 * i + 1];
-  }
-  red[0][tid] = s0;
-  red[1][tid] = s1;
-  __syncthreads();
-  for (int n = 128; n >= 1; n >>= 1) {
-    if (tid < n) {
-      red[0][tid] += red[0][tid + n];
-      red[1][tid] += red[1][tid + n];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
+  const int b = blockIdx.x;
+  img_reduce_partials<2>(part + (long long)b * ntiles * 2, ntiles, red);
+  if (threadIdx.x == 0) {
     out[2 * b] = red[0][0];
     out[2 * b + 1] = red[1][0] / count;
   }
@@ -257,28 +236,10 @@ struct MsFinish {
 // workgroup (l, b): out[b] = (sse, ssim_0, cs_0, ..., ssim_4, cs_4), the sums of level l in the order of k_image_metrics_finish
 __global__ __launch_bounds__(256) void k_msssim_finish(const double* __restrict__ part, MsFinish f, double* __restrict__ out) {
   __shared__ double red[3][256];
-  const int tid = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
+  const int l = blockIdx.x, b = blockIdx.y;
   const int ntiles = f.ntiles[l];
-  const double* p = part + f.off[l] + (long long)b * ntiles * 3;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (int i = tid; i < ntiles; i += 256) {
-    s0 += p[3 * i];
-    s1 += p[3 * i + 1];
-    s2 += p[3 * i + 2];
-  }
-  red[0][tid] = s0;
-  red[1][tid] = s1;
-  red[2][tid] = s2;
-  __syncthreads();
-  for (int n = 128; n >= 1; n >>= 1) {
-    if (tid < n) {
-      red[0][tid] += red[0][tid + n];
-      red[1][tid] += red[1][tid + n];
-      red[2][tid] += red[2][tid + n];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
+  img_reduce_partials<3>(part + f.off[l] + (long long)b * ntiles * 3, ntiles, red);
+  if (threadIdx.x == 0) {
     double* o = out + (long long)b * (1 + 2 * MS_LEVELS);
     if (l == 0) o[0] = red[0][0];
     o[1 + 2 * l] = red[1][0] / f.count[l];
@@ -324,19 +285,29 @@ size_t cfen_image_metrics_bytes_impl(int B, int C, int H, int W) {
   return (size_t)B * (size_t)(metrics_tiles(H, MT_H) * metrics_tiles(W, MT_W)) * 2 * sizeof(double);
 }
 
+// the argument checks of both entry points; `name` is the entry point's and min_edge the smallest image edge it takes
+static int metrics_check_args(const char* name, int min_edge, int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi,
+                              const void* scratch, const double* out) {
+  CFEN_CHECK_ARG(a && b && scratch && out, "%s: null pointer", name);
+  CFEN_CHECK_ARG(u8 == 0 || u8 == 1, "%s: u8 must be 0 ((B,C,H,W) fp32) or 1 ((B,H,W,3) uint8)", name);
+  CFEN_CHECK_ARG(C == 1 || C == 3, "%s: C = %d, must be 1 or 3", name, C);
+  CFEN_CHECK_ARG(!u8 || C == 3, "%s: uint8 images are (B,H,W,3), got C = %d", name, C);
+  if (min_edge == MT_TAPS)
+    CFEN_CHECK_ARG(H >= min_edge && W >= min_edge, "%s: a %d x %d image is smaller than the 11 x 11 SSIM window", name, H, W);
+  else
+    CFEN_CHECK_ARG(H >= min_edge && W >= min_edge,
+                   "%s: a %d x %d image is under %d pixels on a side: the fifth level would be smaller than the 11 x 11 SSIM window", name, H, W, min_edge);
+  CFEN_CHECK_ARG(H <= CFEN_METRICS_MAX_EDGE && W <= CFEN_METRICS_MAX_EDGE, "%s: image size %d x %d over %d", name, H, W, CFEN_METRICS_MAX_EDGE);
+  CFEN_CHECK_ARG(B >= 1 && B <= 65535, "%s: batch %d outside 1 .. 65535", name, B);
+  CFEN_CHECK_ARG(u8 || (hi > lo && hi - lo < 3.0e38f), "%s: the value range (lo, hi) = (%g, %g) is empty or not finite", name, (double)lo, (double)hi);
+  CFEN_CHECK_ARG(cfen_aligned(out, 8) && cfen_aligned(scratch, 8), "%s: out and scratch must be 8-byte aligned (doubles)", name);
+  CFEN_CHECK_ARG(u8 || (cfen_aligned(a, 4) && cfen_aligned(b, 4)), "%s: fp32 images must be 4-byte aligned", name);
+  return CFEN_OK;
+}
+
 int cfen_image_metrics_impl(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
                             hipStream_t s) {
-  CFEN_CHECK_ARG(a && b && scratch && out, "image_metrics: null pointer");
-  CFEN_CHECK_ARG(u8 == 0 || u8 == 1, "image_metrics: u8 must be 0 ((B,C,H,W) fp32) or 1 ((B,H,W,3) uint8)");
-  CFEN_CHECK_ARG(C == 1 || C == 3, "image_metrics: C = %d, must be 1 or 3", C);
-  CFEN_CHECK_ARG(!u8 || C == 3, "image_metrics: uint8 images are (B,H,W,3), got C = %d", C);
-  CFEN_CHECK_ARG(H >= MT_TAPS && W >= MT_TAPS, "image_metrics: a %d x %d image is smaller than the 11 x 11 SSIM window", H, W);
-  CFEN_CHECK_ARG(H <= CFEN_METRICS_MAX_EDGE && W <= CFEN_METRICS_MAX_EDGE, "image_metrics: image size %d x %d over %d", H, W, CFEN_METRICS_MAX_EDGE);
-  CFEN_CHECK_ARG(B >= 1 && B <= 65535, "image_metrics: batch %d outside 1 .. 65535", B);
-  CFEN_CHECK_ARG(u8 || (hi > lo && hi - lo < 3.0e38f), "image_metrics: the value range (lo, hi) = (%g, %g) is empty or not finite", (double)lo, (double)hi);
-  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 7) == 0 && (reinterpret_cast<uintptr_t>(scratch) & 7) == 0,
-                 "image_metrics: out and scratch must be 8-byte aligned (doubles)");
-  CFEN_CHECK_ARG(u8 || ((reinterpret_cast<uintptr_t>(a) & 3) == 0 && (reinterpret_cast<uintptr_t>(b) & 3) == 0), "image_metrics: fp32 images must be 4-byte aligned");
+  if (const int e = metrics_check_args("image_metrics", MT_TAPS, u8, a, b, B, C, H, W, lo, hi, scratch, out)) return e;
   const int nty = (int)metrics_tiles(H, MT_H), ntx = (int)metrics_tiles(W, MT_W);
   const MetricsGeom g = {C, H, W, nty, ntx, u8 ? 0.f : lo, u8 ? 1.f : hi - lo};
   const dim3 grid((unsigned)(nty * ntx), (unsigned)B);
@@ -360,18 +331,7 @@ size_t cfen_image_msssim_bytes_impl(int B, int C, int H, int W) {
 
 int cfen_image_msssim_impl(int u8, const void* a, const void* b, int B, int C, int H, int W, float lo, float hi, void* scratch, double* out,
                            hipStream_t s) {
-  CFEN_CHECK_ARG(a && b && scratch && out, "image_msssim: null pointer");
-  CFEN_CHECK_ARG(u8 == 0 || u8 == 1, "image_msssim: u8 must be 0 ((B,C,H,W) fp32) or 1 ((B,H,W,3) uint8)");
-  CFEN_CHECK_ARG(C == 1 || C == 3, "image_msssim: C = %d, must be 1 or 3", C);
-  CFEN_CHECK_ARG(!u8 || C == 3, "image_msssim: uint8 images are (B,H,W,3), got C = %d", C);
-  CFEN_CHECK_ARG(H >= MS_MIN_EDGE && W >= MS_MIN_EDGE,
-                 "image_msssim: a %d x %d image is under %d pixels on a side: the fifth level would be smaller than the 11 x 11 SSIM window", H, W, MS_MIN_EDGE);
-  CFEN_CHECK_ARG(H <= CFEN_METRICS_MAX_EDGE && W <= CFEN_METRICS_MAX_EDGE, "image_msssim: image size %d x %d over %d", H, W, CFEN_METRICS_MAX_EDGE);
-  CFEN_CHECK_ARG(B >= 1 && B <= 65535, "image_msssim: batch %d outside 1 .. 65535", B);
-  CFEN_CHECK_ARG(u8 || (hi > lo && hi - lo < 3.0e38f), "image_msssim: the value range (lo, hi) = (%g, %g) is empty or not finite", (double)lo, (double)hi);
-  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 7) == 0 && (reinterpret_cast<uintptr_t>(scratch) & 7) == 0,
-                 "image_msssim: out and scratch must be 8-byte aligned (doubles)");
-  CFEN_CHECK_ARG(u8 || ((reinterpret_cast<uintptr_t>(a) & 3) == 0 && (reinterpret_cast<uintptr_t>(b) & 3) == 0), "image_msssim: fp32 images must be 4-byte aligned");
+  if (const int e = metrics_check_args("image_msssim", MS_MIN_EDGE, u8, a, b, B, C, H, W, lo, hi, scratch, out)) return e;
   const MsPlan p = msssim_plan(B, C, H, W);
   double* part = (double*)scratch;
   float* pyr = (float*)(part + p.part_doubles);

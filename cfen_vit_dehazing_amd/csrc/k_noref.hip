@@ -12,12 +12,12 @@
 //                    through a shuffle butterfly and then the four waves in wave order.  One record per workgroup.
 //   k_noref_finish : grid (B, 2, 17).  z < 16: 16 bins x 16 record lanes, a lane adds records lane, lane + 16, ... of its bin in uint64, the 16
 //                    lanes are added through LDS.  z == 16: dark_sum and the saturation count the same way over 256 lanes, and the gradient
-//                    partials in the fixed order of k_ciede2000_finish (thread t takes t, t + 256, ..., then a fixed LDS tree).
+//                    partials in the fixed order of img_reduce_partials (cfen_image.hpp), interleaved with the integer sums.
 // Two launches; no global atomics, no counters; LDS 26.4 KB per workgroup.
 #include <math.h>
 
 #include "../../include/cfen_noref.h"
-#include "cfen_common.hpp"
+#include "cfen_image.hpp"
 
 namespace {
 
@@ -45,12 +45,6 @@ union NrBytes {
   unsigned u[3];
   unsigned char c[12];
 };
-
-CFEN_DEV double nr_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);      // butterfly: every lane ends with the bitwise identical total
-  return v;
-}
 
 CFEN_DEV unsigned nr_min3(unsigned a, unsigned b, unsigned c) { return min(a, min(b, c)); }
 
@@ -162,8 +156,8 @@ __global__ __launch_bounds__(256) void k_noref(const unsigned char* __restrict__
   }
   atomicAdd(&isum[2], sat_in);
   atomicAdd(&isum[3], sat_new);
-  g0 = nr_wave_sum(g0);
-  g1 = nr_wave_sum(g1);
+  g0 = wave_sum(g0);
+  g1 = wave_sum(g1);
   if ((tid & 63) == 0) {
     red[0][tid >> 6] = g0;
     red[1][tid >> 6] = g1;
@@ -175,7 +169,7 @@ __global__ __launch_bounds__(256) void k_noref(const unsigned char* __restrict__
   if (tid < 2) {
     o->cnt[tid][256] = isum[tid];
     o->cnt[tid][257] = isum[2 + tid];
-    o->grad[tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+    o->grad[tid] = block4_sum(red[tid], 1);
   }
 }
 
@@ -246,8 +240,7 @@ extern "C" int cfen_noref_u8(const unsigned char* hazy, const unsigned char* out
   CFEN_CHECK_ARG(B >= 1 && B <= NR_MAX_BATCH, "noref_u8: B = %d outside 1 .. %d", B, NR_MAX_BATCH);
   CFEN_CHECK_ARG(H >= 1 && W >= 1 && H <= NR_MAX_EDGE && W <= NR_MAX_EDGE, "noref_u8: sizes H = %d, W = %d outside 1 .. %d", H, W, NR_MAX_EDGE);
   CFEN_CHECK_ARG(radius >= 0 && radius <= NR_MAXR, "noref_u8: radius = %d outside 0 .. %d", radius, NR_MAXR);
-  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 7) == 0 && (reinterpret_cast<uintptr_t>(counts) & 7) == 0 &&
-                     (reinterpret_cast<uintptr_t>(grad) & 7) == 0,
+  CFEN_CHECK_ARG(cfen_aligned(scratch, 8) && cfen_aligned(counts, 8) && cfen_aligned(grad, 8),
                  "noref_u8: scratch, counts and grad must be 8-byte aligned (64-bit words)");
   const int tiles_x = nr_tiles_x(W), ntiles = tiles_x * nr_tiles_y(H);
   hipStream_t s = (hipStream_t)stream;

@@ -23,7 +23,7 @@
 //        term is known from the strip's index, so it is a plain sum -- and writes the closing block, the checksum and the stream's length.
 //
 // No global atomics and no arrival counters, integer arithmetic only: the same image gives the same bytes on every call, stream and batch size.
-#include "cfen_common.hpp"
+#include "cfen_image.hpp"
 
 namespace {
 
@@ -38,12 +38,6 @@ struct PngGeom {
   int H, W, R, S, rowb, ntab;
   long long strip_stride, out_stride;
 };
-
-CFEN_DEV unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 CFEN_DEV unsigned abs_residual(int v) {
   v &= 255;
@@ -91,11 +85,11 @@ __global__ __launch_bounds__(256) void k_png_deflate(const unsigned char* __rest
       s3 += abs_residual(x - ((a + u) >> 1));
       s4 += abs_residual(x - paeth(a, u, c));
     }
-    s0 = wave_sum_u32(s0);                                       // a lane's sum stays under 128 * 32768 / 64, the wave's under 2^22
-    s1 = wave_sum_u32(s1);
-    s2 = wave_sum_u32(s2);
-    s3 = wave_sum_u32(s3);
-    s4 = wave_sum_u32(s4);
+    s0 = wave_sum(s0);                                           // a lane's sum stays under 128 * 32768 / 64, the wave's under 2^22
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    s3 = wave_sum(s3);
+    s4 = wave_sum(s4);
     int type = 0;
     unsigned best = s0;
     if (s1 < best) best = s1, type = 1;
@@ -144,10 +138,10 @@ __global__ __launch_bounds__(256) void k_png_deflate(const unsigned char* __rest
         c = h * ((t[PNG_TABLE_CODES_AT + tid] >> 16) & 15u);
         if (tid == 0) c += ((t[PNG_TABLE_CODES_AT + 256] >> 16) & 15u) + min(t[0], (unsigned)(32 * PNG_TABLE_HEADER_WORDS));
       }
-      cost[k] = wave_sum_u32(c);
+      cost[k] = wave_sum(c);
     }
   }
-  const unsigned sum_a = wave_sum_u32(adler_a), sum_b = wave_sum_u32(adler_b);     // <= 64 * 33660 and 64 * 65520
+  const unsigned sum_a = wave_sum(adler_a), sum_b = wave_sum(adler_b);             // <= 64 * 33660 and 64 * 65520
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < PNG_MAX_TABLES; ++k) red[wave][k] = cost[k];

@@ -33,13 +33,18 @@ def psnr_from_sse(sse, n_values):
     return float("inf") if sse == 0 else 10.0 * math.log10(255.0 ** 2 * n_values / sse)
 
 
+def _need_cuda(what, *tensors):
+    import torch
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
+        raise ValueError("%s needs CUDA tensors; there is no CPU fallback" % what)
+
+
 def psnr_ssim(out, gt, value_range=(-1.0, 1.0)):
     """[(psnr, ssim), ...] per image, Python floats.  out, gt: (B,H,W,3) / (H,W,3) uint8 or (B,C,H,W) / (C,H,W) float32 CUDA tensors of equal shape;
     value_range maps float images to [0,1] (ignored for uint8).  One device pass and one copy of 16 B bytes back."""
     import torch
     from . import ops
-    if not isinstance(out, torch.Tensor) or not isinstance(gt, torch.Tensor) or not out.is_cuda or not gt.is_cuda:
-        raise ValueError("psnr_ssim needs CUDA tensors; there is no CPU fallback")
+    _need_cuda("psnr_ssim", out, gt)
     sse, ssim = ops.image_metrics(out.contiguous(), gt.contiguous(), value_range=value_range)
     n = out.numel() // sse.numel()
     both = torch.stack([sse, ssim], dim=1).cpu().tolist()
@@ -68,8 +73,7 @@ def psnr_ssim_msssim(out, gt, value_range=(-1.0, 1.0)):
     device call (six launches) and one copy of 88 B bytes back."""
     import torch
     from . import ops
-    if not isinstance(out, torch.Tensor) or not isinstance(gt, torch.Tensor) or not out.is_cuda or not gt.is_cuda:
-        raise ValueError("psnr_ssim_msssim needs CUDA tensors; there is no CPU fallback")
+    _need_cuda("psnr_ssim_msssim", out, gt)
     buf = torch.empty(out.shape[0] if out.dim() == 4 else 1, 11, dtype=torch.float64, device=out.device)
     sse, levels = ops.image_msssim(out.contiguous(), gt.contiguous(), value_range=value_range, out=buf)
     n = out.numel() // sse.numel()
@@ -90,8 +94,7 @@ def ciede2000(out, gt):
     One device call (two launches) and one copy of 8 B bytes back."""
     import torch
     from . import ops
-    if not isinstance(out, torch.Tensor) or not isinstance(gt, torch.Tensor) or not out.is_cuda or not gt.is_cuda:
-        raise ValueError("ciede2000 needs CUDA tensors; there is no CPU fallback")
+    _need_cuda("ciede2000", out, gt)
     return [float(v) for v in ops.image_ciede2000(out.contiguous(), gt.contiguous()).cpu().tolist()]
 
 
@@ -220,8 +223,7 @@ def noref(hazy, out, radius=7):
     launches) and one copy of B * 4160 bytes back."""
     import torch
     from . import ops
-    if not isinstance(hazy, torch.Tensor) or not isinstance(out, torch.Tensor) or not hazy.is_cuda or not out.is_cuda:
-        raise ValueError("noref needs CUDA tensors; there is no CPU fallback")
+    _need_cuda("noref", hazy, out)
     counts, grad = ops.image_noref(hazy.contiguous(), out.contiguous(), radius)
     B = counts.shape[0]
     H, W = (hazy.shape[0], hazy.shape[1]) if hazy.dim() == 3 else (hazy.shape[1], hazy.shape[2])

@@ -526,6 +526,15 @@ def _guided_params(what, radius, eps):
     return r, e * 255.0 * 255.0          # eps is in squared units of the [0, 1] scale; the kernels work on bytes
 
 
+def _field(what, name, t, guide_hi):
+    """the coefficient (or delta) field an apply kernel upsamples to the size of guide_hi"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[3] != 6 or t.dtype != torch.float32 or min(t.shape) < 1 or \
+            t.shape[0] != guide_hi.shape[0] or t.device != guide_hi.device:
+        raise ValueError("%s needs %s as a contiguous (B,h,w,6) float32 tensor for the %d images of guide_hi, got %s"
+                         % (what, name, guide_hi.shape[0], "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+    _cuda(t)
+
+
 def guided_coef_u8(guide_lo, src_lo, radius=2, eps=1e-4, out=None):
     """cfen_guided_coef_u8 (include/cfen_guided.h): the smoothed coefficients of the local linear model src_lo ~ a * guide_lo + b, fitted per pixel
     and channel over a (2 radius + 1)^2 window: (B,h,w,6) float32 = [abar_R, abar_G, abar_B, bbar_R, bbar_G, bbar_B] on the 0..255 scale.
@@ -548,11 +557,7 @@ def guided_apply_u8(coef, guide_hi, out=None):
     to the size of guide_hi (B,H,W,3) uint8 and applied to it: (B,H,W,3) uint8 = clamp(floor(Abar * guide_hi + Bbar + 0.5), 0, 255).  out: the
     caller's (B,H,W,3) uint8 tensor, which may be a lane of a larger slab (no alignment is assumed)."""
     _guided_images("guided_apply_u8", guide_hi=guide_hi)
-    if not isinstance(coef, torch.Tensor) or coef.dim() != 4 or coef.shape[3] != 6 or coef.dtype != torch.float32 or min(coef.shape) < 1 or \
-            coef.shape[0] != guide_hi.shape[0] or coef.device != guide_hi.device:
-        raise ValueError("guided_apply_u8 needs coef as a contiguous (B,h,w,6) float32 tensor for the %d images of guide_hi, got %s"
-                         % (guide_hi.shape[0], "%s %s" % (tuple(coef.shape), coef.dtype) if isinstance(coef, torch.Tensor) else type(coef).__name__))
-    _cuda(coef)
+    _field("guided_apply_u8", "coef", coef, guide_hi)
     B, H, W, _ = guide_hi.shape
     out = _out(out, (B, H, W, 3), torch.uint8, guide_hi.device, "guided_apply_u8")
     check(_lib.load().cfen_guided_apply_u8(ptr(coef), B, coef.shape[1], coef.shape[2], ptr(guide_hi), H, W, ptr(out), current_stream()), "guided_apply_u8")
@@ -621,15 +626,44 @@ def temporal_apply_u8(delta, guide_hi, src_hi, out=None):
     _guided_images("temporal_apply_u8", guide_hi=guide_hi, src_hi=src_hi)
     if guide_hi.shape != src_hi.shape or guide_hi.device != src_hi.device:
         raise ValueError("temporal_apply_u8: guide_hi %s and src_hi %s differ in shape or device" % (tuple(guide_hi.shape), tuple(src_hi.shape)))
-    if not isinstance(delta, torch.Tensor) or delta.dim() != 4 or delta.shape[3] != 6 or delta.dtype != torch.float32 or min(delta.shape) < 1 or \
-            delta.shape[0] != guide_hi.shape[0] or delta.device != guide_hi.device:
-        raise ValueError("temporal_apply_u8 needs delta as a contiguous (B,h,w,6) float32 tensor for the %d images of guide_hi, got %s"
-                         % (guide_hi.shape[0], "%s %s" % (tuple(delta.shape), delta.dtype) if isinstance(delta, torch.Tensor) else type(delta).__name__))
-    _cuda(delta)
+    _field("temporal_apply_u8", "delta", delta, guide_hi)
     B, H, W, _ = guide_hi.shape
     out = _out(out, (B, H, W, 3), torch.uint8, guide_hi.device, "temporal_apply_u8")
     check(_lib.load().cfen_temporal_apply_u8(ptr(delta), B, delta.shape[1], delta.shape[2], ptr(guide_hi), ptr(src_hi), H, W, ptr(out), current_stream()),
           "temporal_apply_u8")
+    return out
+
+
+def _image_pair(what, a, b):
+    """the two images of a full-reference score as a batch: (a, b, u8, B, C, H, W)"""
+    _cuda(a, b)
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
+        raise ValueError("%s: the two images differ in shape, dtype or device: %s %s against %s %s" % (what, tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    u8 = a.dtype == torch.uint8
+    if a.dim() != 4 or (u8 and a.shape[3] != 3) or (not u8 and (a.dtype != torch.float32 or a.shape[1] not in (1, 3))):
+        raise ValueError("%s needs (B,H,W,3) uint8 or (B,1|3,H,W) float32 images, got %s %s" % (what, tuple(a.shape), a.dtype))
+    B, C, H, W = (a.shape[0], 3, a.shape[1], a.shape[2]) if u8 else tuple(a.shape)
+    return a, b, u8, B, C, H, W
+
+
+def _f64_scratch(nbytes, device):
+    """a kernel's scratch of doubles (it goes back to torch's allocator on the stream it was used on)"""
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
+
+
+def _image_pair_scores(what, ncol, a, b, value_range, out):
+    """cfen_<what> on the pair (a, b): the (B, ncol) float64 tensor of its results"""
+    a, b, u8, B, C, H, W = _image_pair(what, a, b)
+    lib = _lib.load()
+    scratch = _f64_scratch(getattr(lib, "cfen_%s_bytes" % what)(B, C, H, W), a.device)
+    if out is None:
+        out = torch.empty(B, ncol, dtype=torch.float64, device=a.device)
+    elif tuple(out.shape) != (B, ncol) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous (%d, %d) float64 CUDA tensor" % (what, B, ncol))
+    lo, hi = value_range
+    check(getattr(lib, "cfen_" + what)(int(u8), ptr(a), ptr(b), B, C, H, W, float(lo), float(hi), ptr(scratch), ptr(out), current_stream()), what)
     return out
 
 
@@ -640,25 +674,8 @@ def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     image without the batch dimension is taken as a batch of one.  ssim is the reference's pytorch_msssim.ssim(window_size=11, val_range=1): Gaussian
     window, valid convolution, mean over channels and window positions.  sse is the sum of squared differences on the 0..255 scale over all values
     (exact for uint8); metrics.psnr_from_sse turns it into PSNR.  H, W >= 11."""
-    _cuda(a, b)
-    if a.dim() == 3:
-        a, b = a[None], b[None]
-    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
-        raise ValueError("image_metrics: the two images differ in shape, dtype or device: %s %s against %s %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
-    u8 = a.dtype == torch.uint8
-    if a.dim() != 4 or (u8 and a.shape[3] != 3) or (not u8 and (a.dtype != torch.float32 or a.shape[1] not in (1, 3))):
-        raise ValueError("image_metrics needs (B,H,W,3) uint8 or (B,1|3,H,W) float32 images, got %s %s" % (tuple(a.shape), a.dtype))
-    B, C, H, W = (a.shape[0], 3, a.shape[1], a.shape[2]) if u8 else tuple(a.shape)
-    lib = _lib.load()
-    nbytes = lib.cfen_image_metrics_bytes(B, C, H, W)
-    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=a.device)
-    if out is None:
-        out = torch.empty(B, 2, dtype=torch.float64, device=a.device)
-    elif tuple(out.shape) != (B, 2) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("image_metrics: out must be a contiguous (%d, 2) float64 CUDA tensor" % B)
-    lo, hi = value_range
-    check(lib.cfen_image_metrics(int(u8), ptr(a), ptr(b), B, C, H, W, float(lo), float(hi), ptr(scratch), ptr(out), current_stream()), "image_metrics")
-    return out[:, 0], out[:, 1]      # (scratch goes back to torch's allocator on the stream it was used on)
+    out = _image_pair_scores("image_metrics", 2, a, b, value_range, out)
+    return out[:, 0], out[:, 1]
 
 
 def image_msssim(a, b, value_range=(-1.0, 1.0), out=None):
@@ -668,24 +685,7 @@ def image_msssim(a, b, value_range=(-1.0, 1.0), out=None):
 
     a, b, value_range: as for image_metrics; min(H, W) >= 176.  sse and levels[:, 0, 0] are bitwise what image_metrics returns for the same input.
     out: a contiguous (B, 11) float64 CUDA tensor to write into (sse, then the ten level values); the results are views of it."""
-    _cuda(a, b)
-    if a.dim() == 3:
-        a, b = a[None], b[None]
-    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
-        raise ValueError("image_msssim: the two images differ in shape, dtype or device: %s %s against %s %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
-    u8 = a.dtype == torch.uint8
-    if a.dim() != 4 or (u8 and a.shape[3] != 3) or (not u8 and (a.dtype != torch.float32 or a.shape[1] not in (1, 3))):
-        raise ValueError("image_msssim needs (B,H,W,3) uint8 or (B,1|3,H,W) float32 images, got %s %s" % (tuple(a.shape), a.dtype))
-    B, C, H, W = (a.shape[0], 3, a.shape[1], a.shape[2]) if u8 else tuple(a.shape)
-    lib = _lib.load()
-    nbytes = lib.cfen_image_msssim_bytes(B, C, H, W)
-    scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=a.device)
-    if out is None:
-        out = torch.empty(B, 11, dtype=torch.float64, device=a.device)
-    elif tuple(out.shape) != (B, 11) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("image_msssim: out must be a contiguous (%d, 11) float64 CUDA tensor" % B)
-    lo, hi = value_range
-    check(lib.cfen_image_msssim(int(u8), ptr(a), ptr(b), B, C, H, W, float(lo), float(hi), ptr(scratch), ptr(out), current_stream()), "image_msssim")
+    out = _image_pair_scores("image_msssim", 11, a, b, value_range, out)
     return out[:, 0], out[:, 1:].unflatten(1, (5, 2))
 
 
@@ -718,14 +718,14 @@ def image_ciede2000(a, b, map=None, out=None):
     nbytes = lib.cfen_ciede2000_bytes(B, H, W)
     if nbytes == 0:
         raise ValueError("image_ciede2000: %d images of %d x %d are outside the limits (B <= 65535, H, W <= 65536)" % (B, H, W))
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+    scratch = _f64_scratch(nbytes, a.device)
     if map is True:
         map = torch.empty(B, H, W, dtype=torch.float32, device=a.device)
     elif map is not None:
         map = _out(map, (B, H, W), torch.float32, a.device, "image_ciede2000 (map)")
     out = _out(out, (B,), torch.float64, a.device, "image_ciede2000")
     check(lib.cfen_ciede2000_u8(ptr(a), ptr(b), B, H, W, ptr(_srgb_table(a.device)), ptr(scratch), ptr(map), ptr(out), current_stream()), "image_ciede2000")
-    return out if map is None else (out, map)      # (scratch goes back to torch's allocator on the stream it was used on)
+    return out if map is None else (out, map)
 
 
 NOREF_TILE_W, NOREF_TILE_H = 64, 64      # CFEN_NOREF_TILE_W / _H of include/cfen_noref.h: one workgroup, one scratch record, per tile
@@ -743,6 +743,25 @@ def _noref_images(what, *images):
             raise ValueError("%s: the two images differ in shape or device: %s against %s" % (what, tuple(first.shape), tuple(t.shape)))
 
 
+def _noref(what, hazy, out, radius, map_hazy, map_out):
+    """cfen_noref_u8 on the pairs (hazy, out): (counts, grad, dark_hazy, dark_out), a map that was not asked for None"""
+    _noref_images(what, hazy, out)
+    B, H, W, _ = hazy.shape
+    dev = hazy.device
+    lib = _lib.load()
+    nbytes = lib.cfen_noref_bytes(B, H, W, int(radius))
+    if nbytes == 0:
+        raise ValueError("%s: %d images of %d x %d at radius %s are outside the limits (B <= 65535, H, W <= 65536, radius 0 .. %d)"
+                         % (what, B, H, W, radius, NOREF_MAX_RADIUS))
+    scratch = _f64_scratch(nbytes, dev)
+    counts = torch.empty(B, 2, 259, dtype=torch.int64, device=dev)
+    grad = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    d0 = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if map_hazy else None
+    d1 = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if map_out else None
+    check(lib.cfen_noref_u8(ptr(hazy), ptr(out), B, H, W, int(radius), ptr(scratch), ptr(counts), ptr(grad), ptr(d0), ptr(d1), current_stream()), what)
+    return counts, grad, d0, d1
+
+
 def image_noref(hazy, out, radius=7, maps=False):
     """cfen_noref_u8 (include/cfen_noref.h): the raw no-reference statistics of B pairs (hazy input, dehazed output), as CUDA tensors.
 
@@ -753,21 +772,8 @@ def image_noref(hazy, out, radius=7, maps=False):
     with and without maps, at every batch size and on every stream; metrics.noref_from_stats turns the statistics into scores."""
     if hazy.dim() == 3 and out.dim() == 3:
         hazy, out = hazy[None], out[None]
-    _noref_images("image_noref", hazy, out)
-    B, H, W, _ = hazy.shape
-    lib = _lib.load()
-    nbytes = lib.cfen_noref_bytes(B, H, W, int(radius))
-    if nbytes == 0:
-        raise ValueError("image_noref: %d images of %d x %d at radius %s are outside the limits (B <= 65535, H, W <= 65536, radius 0 .. %d)"
-                         % (B, H, W, radius, NOREF_MAX_RADIUS))
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=hazy.device)
-    counts = torch.empty(B, 2, 259, dtype=torch.int64, device=hazy.device)
-    grad = torch.empty(B, 2, dtype=torch.float64, device=hazy.device)
-    d0 = torch.empty(B, H, W, dtype=torch.uint8, device=hazy.device) if maps else None
-    d1 = torch.empty(B, H, W, dtype=torch.uint8, device=hazy.device) if maps else None
-    check(lib.cfen_noref_u8(ptr(hazy), ptr(out), B, H, W, int(radius), ptr(scratch), ptr(counts), ptr(grad), ptr(d0), ptr(d1), current_stream()),
-          "image_noref")
-    return (counts, grad, d0, d1) if maps else (counts, grad)      # (scratch goes back to torch's allocator on the stream it was used on)
+    counts, grad, d0, d1 = _noref("image_noref", hazy, out, radius, maps, maps)
+    return (counts, grad, d0, d1) if maps else (counts, grad)
 
 
 def dark_channel_u8(images, radius=7):
@@ -777,19 +783,7 @@ def dark_channel_u8(images, radius=7):
     single = images.dim() == 3
     if single:
         images = images[None]
-    _noref_images("dark_channel_u8", images)
-    B, H, W, _ = images.shape
-    lib = _lib.load()
-    nbytes = lib.cfen_noref_bytes(B, H, W, int(radius))
-    if nbytes == 0:
-        raise ValueError("dark_channel_u8: %d images of %d x %d at radius %s are outside the limits (B <= 65535, H, W <= 65536, radius 0 .. %d)"
-                         % (B, H, W, radius, NOREF_MAX_RADIUS))
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=images.device)
-    counts = torch.empty(B, 2, 259, dtype=torch.int64, device=images.device)
-    grad = torch.empty(B, 2, dtype=torch.float64, device=images.device)
-    dark = torch.empty(B, H, W, dtype=torch.uint8, device=images.device)
-    check(lib.cfen_noref_u8(ptr(images), ptr(images), B, H, W, int(radius), ptr(scratch), ptr(counts), ptr(grad), ptr(dark), None, current_stream()),
-          "dark_channel_u8")
+    dark = _noref("dark_channel_u8", images, images, radius, True, False)[2]
     return dark[0] if single else dark
 
 
