@@ -181,6 +181,12 @@ TEMPORAL_SIGNATURES = {
     "cfen_temporal_apply_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
 }
 
+# every symbol include/cfen_motion.h declares: the motion compensation extension, bound beside the other seven
+MOTION_SIGNATURES = {
+    "cfen_motion_search_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "cfen_motion_warp": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -194,7 +200,8 @@ def load():
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()) + \
-            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()) + list(YUV_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()):
+            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()) + list(YUV_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + \
+            list(MOTION_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -634,6 +634,80 @@ def temporal_apply_u8(delta, guide_hi, src_hi, out=None):
     return out
 
 
+def _motion_block(what, block):
+    try:
+        b = int(block)
+    except (TypeError, ValueError, OverflowError):
+        b = None
+    if b is None or b != block or b not in (8, 16, 32):
+        raise ValueError("%s: block must be 8, 16 or 32, got %r" % (what, block))
+    return b
+
+
+def _pair(out):
+    if out is None:
+        return None, None
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError("out must be a pair of tensors")
+    return out
+
+
+def motion_search_u8(guide, prev_guide, block, range, bias, out=None):
+    """cfen_motion_search_u8 (include/cfen_motion.h): per block x block block of each of the B consecutive working-resolution frames guide (B,h,w,3)
+    uint8, the displacement (dy, dx) within +-range at which the previous frame matches best (the smallest 16 SAD + bias (|dy| + |dx|) 3 n_b, ties
+    to the shorter and then the lexicographically smaller vector), in one launch: returns (vec (B,bh,bw,2) int16, sad (B,bh,bw) int32, the
+    winner's SAD).  prev_guide (h,w,3) uint8 is the frame before guide[0].  out: the caller's (vec, sad) pair."""
+    _guided_images("motion_search_u8", guide=guide)
+    B, h, w, _ = guide.shape
+    dev = guide.device
+    if not isinstance(prev_guide, torch.Tensor) or tuple(prev_guide.shape) != (h, w, 3) or prev_guide.dtype != torch.uint8 or prev_guide.device != dev:
+        raise ValueError("motion_search_u8 needs prev_guide as a contiguous (%d,%d,3) uint8 tensor on the device of guide, got %s"
+                         % (h, w, "%s %s" % (tuple(prev_guide.shape), prev_guide.dtype) if isinstance(prev_guide, torch.Tensor) else type(prev_guide).__name__))
+    _cuda(prev_guide)
+    block = _motion_block("motion_search_u8", block)
+    try:
+        r, bi = int(range), int(bias)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("motion_search_u8: range and bias must be integers, got range %r, bias %r" % (range, bias))
+    if r != range or not 1 <= r <= 16:
+        raise ValueError("motion_search_u8: range must be an integer in 1 .. 16, got %r" % (range,))
+    if bi != bias or not 0 <= bi <= 255:
+        raise ValueError("motion_search_u8: bias must be an integer in 0 .. 255, got %r" % (bias,))
+    bh, bw = -(-h // block), -(-w // block)
+    vec, sad = _pair(out)
+    vec = _out(vec, (B, bh, bw, 2), torch.int16, dev, "motion_search_u8")
+    sad = _out(sad, (B, bh, bw), torch.int32, dev, "motion_search_u8")
+    check(_lib.load().cfen_motion_search_u8(ptr(guide), ptr(prev_guide), B, h, w, block, r, bi, ptr(vec), ptr(sad), current_stream()), "motion_search_u8")
+    return vec, sad
+
+
+def motion_warp(vec, prev_guide, state, block, out=None):
+    """cfen_motion_warp (include/cfen_motion.h): the previous working-resolution frame prev_guide (h,w,3) uint8 and the recursion's state (h,w,6)
+    float32 fetched, per pixel, from where its block's vector vec (bh,bw,2) int16 of motion_search_u8 points (coordinates clamped to the
+    frame): returns (prev_out (h,w,3) uint8, state_out (h,w,6) float32).  A pure gather; inputs and outputs must not overlap.  out: the caller's
+    (prev_out, state_out) pair."""
+    if not isinstance(prev_guide, torch.Tensor) or prev_guide.dim() != 3 or prev_guide.shape[2] != 3 or prev_guide.dtype != torch.uint8 or \
+            min(prev_guide.shape) < 1:
+        raise ValueError("motion_warp needs prev_guide as a contiguous (h,w,3) uint8 tensor, got %s"
+                         % ("%s %s" % (tuple(prev_guide.shape), prev_guide.dtype) if isinstance(prev_guide, torch.Tensor) else type(prev_guide).__name__))
+    h, w, _ = prev_guide.shape
+    dev = prev_guide.device
+    block = _motion_block("motion_warp", block)
+    bh, bw = -(-h // block), -(-w // block)
+    if not isinstance(vec, torch.Tensor) or tuple(vec.shape) != (bh, bw, 2) or vec.dtype != torch.int16 or vec.device != dev:
+        raise ValueError("motion_warp needs vec as a contiguous (%d,%d,2) int16 tensor on the device of prev_guide, got %s"
+                         % (bh, bw, "%s %s" % (tuple(vec.shape), vec.dtype) if isinstance(vec, torch.Tensor) else type(vec).__name__))
+    if not isinstance(state, torch.Tensor) or tuple(state.shape) != (h, w, 6) or state.dtype != torch.float32 or state.device != dev:
+        raise ValueError("motion_warp needs state as a contiguous (%d,%d,6) float32 tensor on the device of prev_guide, got %s"
+                         % (h, w, "%s %s" % (tuple(state.shape), state.dtype) if isinstance(state, torch.Tensor) else type(state).__name__))
+    _cuda(vec, prev_guide, state)
+    prev_out, state_out = _pair(out)
+    prev_out = _out(prev_out, (h, w, 3), torch.uint8, dev, "motion_warp")
+    state_out = _out(state_out, (h, w, 6), torch.float32, dev, "motion_warp")
+    check(_lib.load().cfen_motion_warp(ptr(vec), ptr(prev_guide), ptr(state), h, w, block, ptr(prev_out), ptr(state_out), current_stream()), "motion_warp")
+    return prev_out, state_out
+
+
 def _image_pair(what, a, b):
     """the two images of a full-reference score as a batch: (a, b, u8, B, C, H, W)"""
     _cuda(a, b)

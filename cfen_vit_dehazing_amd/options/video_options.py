@@ -36,6 +36,16 @@ class VideoOptions(TestOptions):
                        help='--temporal: regulariser of the local variance, in squared units of the [0, 1] intensity scale, finite and > 0 (default 1e-4)')
         p.add_argument('--temporal_down', type=str, default=None,
                        help='--temporal: integer factor >= 1 between the frame and the working resolution, or auto = ceil(max(H, W) / 1024) (default auto)')
+        p.add_argument('--temporal_mc', type=int, default=None,
+                       help='--temporal: motion compensation (DESIGN section 20): look every block of the working-resolution frame up in the previous '
+                            'frame within +-N pixels, N in 0 .. 16, and let the recursion follow it, so that a moving camera no longer switches the '
+                            'recursion off (default 0 = off; 8 covers a pan of 8 working-resolution pixels per frame)')
+        p.add_argument('--temporal_mc_block', type=int, default=None, choices=(8, 16, 32),
+                       help='--temporal_mc: edge of the matched blocks at the working resolution (default 16)')
+        p.add_argument('--temporal_mc_bias', type=int, default=None,
+                       help='--temporal_mc: preference for short vectors, in sixteenths of a level of mean absolute difference per pixel of displacement, '
+                            '0 .. 255 (default 4). The defaults of the --temporal_mc options come from a synthetic panning experiment on the '
+                            'scattering-model scene (DESIGN section 20), not from a checkpoint')
         for a in p._actions:
             if a.dest == 'dataroot':
                 a.required = False
@@ -47,6 +57,31 @@ class VideoOptions(TestOptions):
     def _without_temporal(text):
         """a run without --temporal prints and records what it always did"""
         return ''.join(l for l in text.splitlines(True) if not l.startswith('temporal'))
+
+    @staticmethod
+    def _without_temporal_mc(text):
+        """a run without --temporal_mc prints and records what it always did"""
+        return ''.join(l for l in text.splitlines(True) if not l.startswith('temporal_mc'))
+
+    def _check_temporal_mc(self, first):
+        """the refusals of the --temporal_mc options; returns the defaults of those not given, as arguments"""
+        from .. import temporal
+        given = {k: getattr(first, 'temporal_' + k) for k in ('mc', 'mc_block', 'mc_bias') if getattr(first, 'temporal_' + k) is not None}
+        if not first.temporal:
+            if given:
+                raise ValueError('%s only applies with --temporal' % ', '.join('--temporal_' + k for k in given))
+            return []
+        mc = given.get('mc', temporal.MC_DEFAULTS['range'])
+        if not 0 <= mc <= 16:
+            raise ValueError('--temporal_mc must be an integer in 0 .. 16 (0 = off), got %d' % mc)
+        if mc == 0 and len(given) > ('mc' in given):
+            raise ValueError('%s only applies with --temporal_mc > 0' % ', '.join('--temporal_' + k for k in given if k != 'mc'))
+        try:
+            temporal.check_mc_params(mc, given.get('mc_block', temporal.MC_DEFAULTS['block']), given.get('mc_bias', temporal.MC_DEFAULTS['bias']), '--temporal')
+        except ValueError as e:
+            raise ValueError(str(e).replace('--temporal: ', '--temporal_', 1))
+        defaults = {'mc': temporal.MC_DEFAULTS['range'], 'mc_block': temporal.MC_DEFAULTS['block'], 'mc_bias': temporal.MC_DEFAULTS['bias']}
+        return [a for k in defaults if k not in given for a in ('--temporal_' + k, str(defaults[k]))]
 
     def _check_temporal(self, first):
         """the refusals of the --temporal options; returns the defaults of those not given, as arguments"""
@@ -83,7 +118,8 @@ class VideoOptions(TestOptions):
             raise ValueError('--eval_noref with --out -: say where noref.csv goes with --noref_csv PATH')
         if first.noref_csv and not first.eval_noref:
             raise ValueError('--noref_csv is where --eval_noref writes: it needs --eval_noref')
-        extra_temporal = self._check_temporal(first)
+        extra_temporal = self._check_temporal(first) + self._check_temporal_mc(first)
+        mc_on = bool(first.temporal and first.temporal_mc)
         # test.py's own checks run on what test.py would be given: frames in order, and --tile there means one image per call.  What that parse
         # prints and records is held back, corrected to the batch size this run really uses, and recorded in a file of its own: opt.txt stays
         # what the last test.py run of the same --name wrote
@@ -100,12 +136,14 @@ class VideoOptions(TestOptions):
             opt.temporal_down = int(opt.temporal_down)
         text = held.getvalue().replace('\nbatchSize: 1\n', '\nbatchSize: %d\n' % opt.batchSize) if first.tile else held.getvalue()
         text = text if first.temporal else self._without_temporal(text)
+        text = text if mc_on else self._without_temporal_mc(text)
         sys.stdout.write(text)
         sys.stdout.flush()
         if opt.dist_rank == 0:
             try:
                 recorded = open(opt_txt).read()
                 recorded = recorded if first.temporal else self._without_temporal(recorded)
+                recorded = recorded if mc_on else self._without_temporal_mc(recorded)
                 if before is None:
                     os.remove(opt_txt)
                 else:

@@ -332,10 +332,15 @@ def run(opt, log=print):
     stabiliser = None
     if getattr(opt, "temporal", False):
         from . import temporal
-        stabiliser = temporal.Stabiliser(opt.temporal_radius, opt.temporal_eps, opt.temporal_strength, opt.temporal_motion, opt.temporal_down)
+        mc = getattr(opt, "temporal_mc", None) or 0
+        stabiliser = temporal.Stabiliser(opt.temporal_radius, opt.temporal_eps, opt.temporal_strength, opt.temporal_motion, opt.temporal_down,
+                                         **(dict(mc_range=mc, mc_block=opt.temporal_mc_block, mc_bias=opt.temporal_mc_bias) if mc else {}))
         S, h, w = temporal.working_size(H, W, stabiliser.down)
         log("video: temporal stabilisation at %d x %d (1/%d), radius %d, eps %g, strength %g, motion %g levels"
             % (w, h, S, stabiliser.radius, stabiliser.eps, stabiliser.strength, stabiliser.motion))
+        if mc:
+            log("video: motion compensation within +-%d pixels, blocks of %d x %d, bias %d / 16 levels per pixel"
+                % (stabiliser.mc_range, stabiliser.mc_block, stabiliser.mc_block, stabiliser.mc_bias))
 
     def through_model(x, first):
         """the model's own batch route, the one test.py takes (the half guard included where test.py applies it)"""
