@@ -654,6 +654,9 @@ __global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg,
   const bool live = row < M;
   const int nvec = D / EPL;
   const T* x = X + (live ? row : 0) * D;
+  // the row is held as v - p, p = its first element: the sum that gives the mean is then of the size of the row's spread, and mean - p carries no
+  // rounding of the size of the mean itself (a row of 1 +- 0.01 lost a digit of its normalised values to the rounding of a sum near D)
+  const float p = (float)x[0];
   float v[MAXV][EPL];
   float sum = 0.f;
 #pragma unroll
@@ -662,11 +665,12 @@ __global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg,
     if (idx < nvec) {
       Vec16<T>::load(x + idx * EPL, v[i]);
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) sum += v[i][e];
+      for (int e = 0; e < EPL; ++e) { v[i][e] -= p; sum += v[i][e]; }
     }
   }
   sum = group_sum<G>(sum);
-  const float mean = sum / (float)Dn;
+  sum += (float)(D - Dn) * p;                       // the zero slots each added 0 - p
+  const float mean = sum / (float)Dn;               // of v - p
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
@@ -680,7 +684,7 @@ __global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg,
     }
   }
   sq = group_sum<G>(sq);
-  sq -= (float)(D - Dn) * mean * mean;              // the zero slots each added (0 - mean)^2
+  sq -= (float)(D - Dn) * (p + mean) * (p + mean);  // the zero slots each added (0 - p - mean)^2
   const float rstd = rsqrtf(fmaxf(sq, 0.f) / (float)Dn + eps);
   if (!live) return;
   T* y = Y + row * D;

@@ -481,25 +481,39 @@ int launch_conv(int ng, const ConvDesc* dp, hipStream_t s) {
 // Per-(image, channel) statistics of x0 (+x1 +x2): sum, sum of squares, max -- partial results per
 // pixel chunk, finished by the consumer.  Serves InstanceNorm2d (v3:292-302) and CFSM2G's global
 // average / max pools (v3:1503-1505).
+// The sums are those of x - p and (x - p)^2, p = the channel's value at the image's first pixel (every chunk of the image reads the same one):
+// they are of the size of the channel's spread, not of its mean, so the consumers' variance q/n - (s/n)^2 does not cancel (the fp32 sum of
+// x^2 of a channel at mean 256 and unit spread has lost the spread, whatever precision finishes it).  A chunk's record is ST_ROWS rows of C
+// floats: sum, sum of squares, max, p.
 constexpr int ST_CHUNKS = 64;
+constexpr int ST_ROWS = 4;
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_chan_stats(const T* __restrict__ x0, const T* __restrict__ x1, const T* __restrict__ x2,
                                                     float* __restrict__ part, int HW, int C, int cs) {
   constexpr int EPL = Vec16<T>::N;
   __shared__ float red[3][256][EPL + 1];
+  __shared__ float piv[128];
   const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
   const int cv = C / EPL;                       // channel vectors
   const int lanes_per_cv = 256 / cv;            // threads sharing one channel vector
   const int my_cv = tid % cv, my_p = tid / cv;
   const int per = (HW + ST_CHUNKS - 1) / ST_CHUNKS;
   const int p0 = chunk * per, p1 = min(HW, p0 + per);
-  float s[EPL], q[EPL], m[EPL];
+  float s[EPL], q[EPL], m[EPL], pv[EPL];
 #pragma unroll
-  for (int e = 0; e < EPL; ++e) { s[e] = 0.f; q[e] = 0.f; m[e] = -3.0e38f; }
+  for (int e = 0; e < EPL; ++e) { s[e] = 0.f; q[e] = 0.f; m[e] = -3.0e38f; pv[e] = 0.f; }
   if (my_p < lanes_per_cv) {
     // four pixels per pass, their 4 (or 12) vector loads issued before the first add (clamped to the last pixel past the end of the chunk)
     typedef typename Mma<T>::frag frag;
+    {
+      const size_t o0 = (size_t)b * HW * cs + my_cv * EPL;   // the image's first pixel
+      const frag g0 = load_frag<T>(x0 + o0);
+      frag g1 = g0, g2 = g0;
+      if (x1) { g1 = load_frag<T>(x1 + o0); g2 = load_frag<T>(x2 + o0); }
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) pv[e] = x1 ? ((float)g0[e] + (float)g1[e]) + (float)g2[e] : (float)g0[e];
+    }
     constexpr int U = 4;
     for (int pb = p0 + my_p; pb < p1; pb += U * lanes_per_cv) {
       frag f0[U], f1[U], f2[U];
@@ -523,13 +537,17 @@ __global__ __launch_bounds__(256) void k_chan_stats(const T* __restrict__ x0, co
         for (int e = 0; e < EPL; ++e) {
           float v = (float)f0[u][e];
           if (x1) v = (v + (float)f1[u][e]) + (float)f2[u][e];
-          s[e] += v; q[e] += v * v; m[e] = fmaxf(m[e], v);
+          const float c = v - pv[e];
+          s[e] += c; q[e] += c * c; m[e] = fmaxf(m[e], v);
         }
       }
     }
   }
 #pragma unroll
   for (int e = 0; e < EPL; ++e) { red[0][tid][e] = s[e]; red[1][tid][e] = q[e]; red[2][tid][e] = m[e]; }
+  if (tid < cv)                                  // (my_p == 0: the thread has loaded its channel vector's p)
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) piv[tid * EPL + e] = pv[e];
   __syncthreads();
   if (tid < C) {
     const int vcol = tid / EPL, e = tid % EPL;
@@ -538,8 +556,8 @@ __global__ __launch_bounds__(256) void k_chan_stats(const T* __restrict__ x0, co
       int src = k * cv + vcol;
       ss += red[0][src][e]; qq += red[1][src][e]; mm = fmaxf(mm, red[2][src][e]);
     }
-    float* o = part + (((size_t)b * ST_CHUNKS + chunk) * 3) * C;
-    o[tid] = ss; o[C + tid] = qq; o[2 * C + tid] = mm;
+    float* o = part + (((size_t)b * ST_CHUNKS + chunk) * ST_ROWS) * C;
+    o[tid] = ss; o[C + tid] = qq; o[2 * C + tid] = mm; o[3 * C + tid] = piv[tid];
   }
 }
 
@@ -558,7 +576,7 @@ __global__ __launch_bounds__(256) void k_instnorm_relu(T* __restrict__ x, const 
     double s = 0.0, q = 0.0;
 #pragma unroll 4
     for (int k = sub; k < ST_CHUNKS; k += tpc) {
-      const float* o = part + (((size_t)b * ST_CHUNKS + k) * 3) * C;
+      const float* o = part + (((size_t)b * ST_CHUNKS + k) * ST_ROWS) * C;
       s += (double)o[cc]; q += (double)o[C + cc];
     }
     ps_l[tid] = s; pq_l[tid] = q;
@@ -567,10 +585,10 @@ __global__ __launch_bounds__(256) void k_instnorm_relu(T* __restrict__ x, const 
   if (tid < C) {
     double s = 0.0, q = 0.0;
     for (int k = 0; k < tpc; ++k) { s += ps_l[k * C + tid]; q += pq_l[k * C + tid]; }
-    double mean = s / HW;
-    double var = q / HW - mean * mean;
+    const double ms = s / HW;                    // mean - p (k_chan_stats)
+    double var = q / HW - ms * ms;
     if (var < 0.0) var = 0.0;
-    mean_l[tid] = (float)mean;
+    mean_l[tid] = (float)((double)part[(((size_t)b * ST_CHUNKS) * ST_ROWS + 3) * C + tid] + ms);
     rstd_l[tid] = (float)(1.0 / sqrt(var + (double)eps));
   }
   __syncthreads();
@@ -621,7 +639,7 @@ __global__ __launch_bounds__(256) void k_cfsm_apply(const T* __restrict__ x0, co
     float m = -3.0e38f;
 #pragma unroll 4
     for (int k = sub; k < ST_CHUNKS; k += tpc) {
-      const float* o = part + (((size_t)b * ST_CHUNKS + k) * 3) * C;
+      const float* o = part + (((size_t)b * ST_CHUNKS + k) * ST_ROWS) * C;
       s += (double)o[cc];
       m = fmaxf(m, o[2 * C + cc]);
     }
@@ -632,7 +650,7 @@ __global__ __launch_bounds__(256) void k_cfsm_apply(const T* __restrict__ x0, co
     double s = 0.0;
     float m = -3.0e38f;
     for (int k = 0; k < tpc; ++k) { s += ps_l[k * C + tid]; m = fmaxf(m, pm_l[k * C + tid]); }
-    avg_l[tid] = (float)(s / HW);
+    avg_l[tid] = (float)((double)part[(((size_t)b * ST_CHUNKS) * ST_ROWS + 3) * C + tid] + s / HW);   // sums are of x - p
     max_l[tid] = m;
   }
   __syncthreads();
@@ -695,15 +713,22 @@ __global__ __launch_bounds__(128) void k_actnorm_finalize(const float* __restric
   const int c = threadIdx.x;
   if (c >= Cpad) return;
   if (c >= C) { scale[c] = 0.f; shift[c] = 0.f; an_out[c] = 0.f; an_out[Cpad + c] = 0.f; return; }
+  // every image's sums are about its own p (k_chan_stats); in double they move to image 0's exactly enough: sum (x - P) = sum (x - p) + HW d,
+  // sum (x - P)^2 = sum (x - p)^2 + 2 d sum (x - p) + HW d^2, d = p - P -- and where d is large, so is the variance it belongs to
+  const double P = (double)part[3 * Cs + c];
   double s = 0.0, q = 0.0;
-  for (int b = 0; b < B; ++b)
+  for (int b = 0; b < B; ++b) {
+    double sb = 0.0, qb = 0.0;
     for (int k = 0; k < ST_CHUNKS; ++k) {
-      const float* o = part + (((size_t)b * ST_CHUNKS + k) * 3) * Cs;   // statistics were taken over the map's Cs (padded) channels
-      s += (double)o[c]; q += (double)o[Cs + c];
+      const float* o = part + (((size_t)b * ST_CHUNKS + k) * ST_ROWS) * Cs;   // statistics were taken over the map's Cs (padded) channels
+      sb += (double)o[c]; qb += (double)o[Cs + c];
     }
+    const double d = (double)part[(((size_t)b * ST_CHUNKS) * ST_ROWS + 3) * Cs + c] - P;
+    s += sb + HW * d; q += qb + 2.0 * d * sb + HW * d * d;
+  }
   const double n = (double)B * HW;
-  const double mean = s / n;
-  double var = (q - s * mean) / (n - 1.0);
+  const double mean = P + s / n;
+  double var = (q - s * (s / n)) / (n - 1.0);
   if (var < 0.2) var = 0.2;
   const float w = (float)(-0.5 * log(var)), bb = (float)(-mean);
   const float sc = expf(w);
@@ -735,7 +760,7 @@ inline unsigned grid_img(long long nvec) {
 
 }  // namespace
 
-size_t cfen_stats_workspace_bytes(int B, int C) { return (size_t)B * ST_CHUNKS * 3 * C * sizeof(float); }
+size_t cfen_stats_workspace_bytes(int B, int C) { return (size_t)B * ST_CHUNKS * ST_ROWS * C * sizeof(float); }
 
 int cfen_conv_impl_g(int dtype, int ng, const ConvDesc* d, hipStream_t s) {
   if (dtype == 1) return launch_conv<half_t>(ng, d, s);

@@ -403,10 +403,15 @@ __global__ __launch_bounds__(256, (TN > 3 && NS == 2) ? 2 : 1) void k_gemm_dma(G
 #pragma unroll
   for (int st = 0; st < NS - 1; ++st)
     if (st < nk) CFEN_GEMM_DMA_ISSUE(st, st);
-  // LN-fold: thread (row = tid / 8 (+ 32 per extra token tile), piece = tid % 8) sums x and x^2 of its 16 bytes of every staged X tile
-  float ls[TM], lq[TM];
+  // LN-fold: thread (row = tid / 8 (+ 32 per extra token tile), piece = tid % 8) sums x - p and (x - p)^2 of its 16 bytes of every staged X tile.
+  // p = the row's first element, read from memory by every lane and every K slice alike, so the slices' sums add up: the variance comes out of
+  // sums of the size of the row's spread, not of its mean (E[x^2] - mean^2 from fp32 sums has lost a unit variance at a mean of a few hundred)
+  float ls[TM], lq[TM], lp[TM];
 #pragma unroll
-  for (int j = 0; j < TM; ++j) ls[j] = lq[j] = 0.f;
+  for (int j = 0; j < TM; ++j) {
+    ls[j] = lq[j] = 0.f;
+    lp[j] = a.lnf_s ? (float)a.X[(size_t)min(m0 + (tid >> 3) + 32 * j, a.M - 1) * a.ldx] : 0.f;   // (the fold takes a plain token matrix: no gather)
+  }
   const int lnoff = (G_BN + (tid >> 3)) * G_BKB + (tid & 7) * 16;
   int buf = 0, fill = NS - 1;   // ring slots: `buf` is consumed at this step, `fill` receives K-step kt + NS - 1
   for (int kt = 0; kt < nk; ++kt) {
@@ -426,7 +431,7 @@ __global__ __launch_bounds__(256, (TN > 3 && NS == 2) ? 2 : 1) void k_gemm_dma(G
         float v[EPL];
         Vec16<T>::load(reinterpret_cast<const T*>(st + lnoff + j * 32 * G_BKB), v);
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) { ls[j] += v[e]; lq[j] += v[e] * v[e]; }
+        for (int e = 0; e < EPL; ++e) { const float c = v[e] - lp[j]; ls[j] += c; lq[j] += c * c; }
       }
     }
 #pragma unroll
@@ -441,7 +446,13 @@ __global__ __launch_bounds__(256, (TN > 3 && NS == 2) ? 2 : 1) void k_gemm_dma(G
 #pragma unroll
       for (int i = 0; i < TN; ++i)
 #pragma unroll
-        for (int j = 0; j < TM; ++j) acc[i][j] = Mma<T>::mma(af[i], bf[j], acc[i][j]);
+        for (int j = 0; j < TM; ++j) {
+          // fp32: the chunk's 16 products are summed from zero and added to the accumulator once -- K / 16 additions at the accumulator's
+          // magnitude instead of K (one chain of 1536 MFMA additions sat 3 .. 5 times further from float64 than a blocked product, which at a
+          // row mean of 64 spreads was the whole error of the LayerNorm fold).  fp16: one MFMA per chunk as before, the same bits.
+          if constexpr (sizeof(T) == 4) acc[i][j] += Mma<T>::mma(af[i], bf[j], floatx4{0.f, 0.f, 0.f, 0.f});
+          else acc[i][j] = Mma<T>::mma(af[i], bf[j], acc[i][j]);
+        }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of `buf` are complete before it reaches the next barrier
     fill = buf;
@@ -457,7 +468,7 @@ __global__ __launch_bounds__(256, (TN > 3 && NS == 2) ? 2 : 1) void k_gemm_dma(G
     constexpr int NV = TN * TM;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     const int tile = tm * a.map.gn + tn;
-    const size_t slab = (size_t)(NV * 4 + 2 * TM) * 256;   // floats per (tile, slice): NV accumulator vectors, then (sum, sum of squares) per token tile
+    const size_t slab = (size_t)(NV * 4 + 2 * TM) * 256;   // floats per (tile, slice): NV accumulator vectors, then (sum, sum of squares) of x - p per token tile
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(a.part, 0, -1, 0x00020000);
     const unsigned pbase = (unsigned)(((size_t)tile * a.nsplit + blockIdx.y) * slab * 4);   // byte offset of this slice's slab (< 2^32: checked on the host)
 #pragma unroll
@@ -526,9 +537,9 @@ __global__ __launch_bounds__(256, (TN > 3 && NS == 2) ? 2 : 1) void k_gemm_dma(G
       sv += dpp_mov<0x4E>(sv); qv += dpp_mov<0x4E>(qv);
       sv += dpp_mov<0x141>(sv); qv += dpp_mov<0x141>(qv);
       if ((tid & 7) == 0) {
-        const float mean = sv / (float)a.K;
-        const float var = fmaxf(qv / (float)a.K - mean * mean, 0.f);
-        stats[2 * ((tid >> 3) + 32 * j)] = mean;
+        const float ms = sv / (float)a.K;            // mean - p
+        const float var = fmaxf(qv / (float)a.K - ms * ms, 0.f);
+        stats[2 * ((tid >> 3) + 32 * j)] = lp[j] + ms;
         stats[2 * ((tid >> 3) + 32 * j) + 1] = rsqrtf(var + a.lnf_eps);
       }
     }

@@ -149,7 +149,9 @@ __global__ __launch_bounds__(512) void k_gvit_chain(Grouped<GvArgs> ga) {
       floatx4 acc[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
-      float ls[2] = {0.f, 0.f}, lq[2] = {0.f, 0.f};
+      // LN-fold sums of x - p and (x - p)^2, p = the row's first element (taken from the first staged tile: a folded phase is not split over K):
+      // sums of the size of the row's spread, not of its mean -- see k_gemm_dma
+      float ls[2] = {0.f, 0.f}, lq[2] = {0.f, 0.f}, lp[2] = {0.f, 0.f};
       const int lnoff = (tid >> 3) * 128 + (tid & 7) * 16;   // + 64 rows for the second piece
       const int sw = r16 & 7;
       int buf = 0, fill = GV_NS - 1;
@@ -162,8 +164,10 @@ __global__ __launch_bounds__(512) void k_gvit_chain(Grouped<GvArgs> ga) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             const half8 v = *reinterpret_cast<const half8*>(st + lnoff + j * 64 * 128);
+            // piece 0 of row r sits in slot r & 7 of its 128-byte line (the DMA's swizzle)
+            if (kt == 0) lp[j] = (float)*reinterpret_cast<const half_t*>(st + ((tid >> 3) + j * 64) * 128 + (((tid >> 3) & 7) << 4));
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; ls[j] += f; lq[j] += f * f; }
+            for (int e = 0; e < 8; ++e) { const float f = (float)v[e] - lp[j]; ls[j] += f; lq[j] += f * f; }
           }
         }
         if (!(dbg & 4))
@@ -227,9 +231,9 @@ __global__ __launch_bounds__(512) void k_gvit_chain(Grouped<GvArgs> ga) {
           sv += dpp_mov<0x4E>(sv); qv += dpp_mov<0x4E>(qv);
           sv += dpp_mov<0x141>(sv); qv += dpp_mov<0x141>(qv);
           if ((tid & 7) == 0) {
-            const float mean = sv / (float)ph.K;
-            const float var = fmaxf(qv / (float)ph.K - mean * mean, 0.f);
-            stats[2 * ((tid >> 3) + 64 * j)] = mean;
+            const float ms = sv / (float)ph.K;          // mean - p
+            const float var = fmaxf(qv / (float)ph.K - ms * ms, 0.f);
+            stats[2 * ((tid >> 3) + 64 * j)] = lp[j] + ms;
             stats[2 * ((tid >> 3) + 64 * j) + 1] = rsqrtf(var + a.eps);
           }
         }
