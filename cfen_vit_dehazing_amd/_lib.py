@@ -187,6 +187,12 @@ MOTION_SIGNATURES = {
     "cfen_motion_warp": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
 }
 
+# every symbol include/cfen_flicker.h declares: the flicker-along-the-motion extension, bound beside the other eight
+FLICKER_SIGNATURES = {
+    "cfen_flicker_bytes": (c_size_t, [_I, _I, _I]),
+    "cfen_flicker_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -201,7 +207,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()) + \
             list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()) + list(YUV_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + \
-            list(MOTION_SIGNATURES.items()):
+            list(MOTION_SIGNATURES.items()) + list(FLICKER_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -741,6 +741,47 @@ def _image_pair_scores(what, ncol, a, b, value_range, out):
     return out
 
 
+def flicker_u8(guide, prev_guide, tgt, prev_tgt, vec, block, tol, out=None):
+    """cfen_flicker_u8 (include/cfen_flicker.h): the integer sums behind the flicker along the motion of B consecutive working-resolution frames.
+    guide, tgt (B,h,w,3) uint8: the hazy frames and the frames scored; prev_guide, prev_tgt (h,w,3) uint8: the frames before guide[0] and tgt[0];
+    vec None (the zero field) or (B,bh,bw,2) int16 as ops.motion_search_u8 writes it; block 8, 16 or 32; tol 0 .. 255.  tgt may be guide and
+    prev_tgt prev_guide.  Returns (B,8) int64: n_cov, n_match, sum_matched dI, sum_matched dF, sum_matched eF, sum_covered dF, sum_covered dI, 0;
+    flicker.scores_from_sums turns them into scores.  Two launches; the same bits at every batch size and on every stream.  out: the caller's
+    (B,8) int64 tensor."""
+    _guided_images("flicker_u8", guide=guide, tgt=tgt)
+    B, h, w, _ = guide.shape
+    dev = guide.device
+    if tgt.shape != guide.shape or tgt.device != dev:
+        raise ValueError("flicker_u8: guide %s and tgt %s differ in shape or device" % (tuple(guide.shape), tuple(tgt.shape)))
+    for name, t in (("prev_guide", prev_guide), ("prev_tgt", prev_tgt)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (h, w, 3) or t.dtype != torch.uint8 or t.device != dev:
+            raise ValueError("flicker_u8 needs %s as a contiguous (%d,%d,3) uint8 tensor on the device of guide, got %s"
+                             % (name, h, w, "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+    _cuda(prev_guide, prev_tgt)
+    block = _motion_block("flicker_u8", block)
+    try:
+        tl = int(tol)
+    except (TypeError, ValueError, OverflowError):
+        tl = None
+    if tl is None or tl != tol or not 0 <= tl <= 255:
+        raise ValueError("flicker_u8: tol must be an integer in 0 .. 255, got %r" % (tol,))
+    bh, bw = -(-h // block), -(-w // block)
+    if vec is not None:
+        if not isinstance(vec, torch.Tensor) or tuple(vec.shape) != (B, bh, bw, 2) or vec.dtype != torch.int16 or vec.device != dev:
+            raise ValueError("flicker_u8 needs vec as None or a contiguous (%d,%d,%d,2) int16 tensor on the device of guide, got %s"
+                             % (B, bh, bw, "%s %s" % (tuple(vec.shape), vec.dtype) if isinstance(vec, torch.Tensor) else type(vec).__name__))
+        _cuda(vec)
+    lib = _lib.load()
+    nbytes = lib.cfen_flicker_bytes(B, h, w)
+    if nbytes == 0:
+        raise ValueError("flicker_u8: %d frames of %d x %d are outside the limits (B <= 65536, h, w <= 16384, at most 2^31 - 1 tiles of 64 x 64)" % (B, h, w))
+    out = _out(out, (B, 8), torch.int64, dev, "flicker_u8")
+    scratch = _f64_scratch(nbytes, dev)
+    check(lib.cfen_flicker_u8(ptr(guide), ptr(prev_guide), ptr(tgt), ptr(prev_tgt), ptr(vec), B, h, w, block, tl, ptr(scratch), ptr(out),
+                              current_stream()), "flicker_u8")
+    return out
+
+
 def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     """cfen_image_metrics: per image pair (sse, ssim) as two float64 CUDA tensors of shape (B,), in one fused pass.
 

@@ -46,6 +46,22 @@ class VideoOptions(TestOptions):
                        help='--temporal_mc: preference for short vectors, in sixteenths of a level of mean absolute difference per pixel of displacement, '
                             '0 .. 255 (default 4). The defaults of the --temporal_mc options come from a synthetic panning experiment on the '
                             'scattering-model scene (DESIGN section 20), not from a checkpoint')
+        p.add_argument('--eval_flicker', action='store_true',
+                       help='(extension) score the flicker of the stream along the motion (DESIGN section 22): per frame pair, how much the '
+                            "network's frames and the frames that leave change where the hazy input, followed along block vectors, did not; "
+                            'writes flicker.csv and prints one summary line. The stream itself is unchanged')
+        p.add_argument('--flicker_range', type=int, default=None,
+                       help='--eval_flicker: the blocks are looked up within +-N working-resolution pixels, N in 0 .. 16 (default 8; 0 compares '
+                            'every pixel with the same pixel of the previous frame)')
+        p.add_argument('--flicker_block', type=int, default=None, choices=(8, 16, 32), help='--eval_flicker: edge of the matched blocks (default 16)')
+        p.add_argument('--flicker_bias', type=int, default=None,
+                       help='--eval_flicker: preference of the search for short vectors, as --temporal_mc_bias, 0 .. 255 (default 4)')
+        p.add_argument('--flicker_tol', type=int, default=None,
+                       help='--eval_flicker: a pixel counts where the hazy bytes changed by at most this many levels per channel on average along '
+                            'its vector, 0 .. 255 (default 8)')
+        p.add_argument('--flicker_down', type=str, default=None,
+                       help='--eval_flicker: integer factor >= 1 between the frame and the working resolution, or auto = ceil(max(H, W) / 1024) (default auto)')
+        p.add_argument('--flicker_csv', type=str, default=None, help='--eval_flicker: where flicker.csv goes (default: beside --out; required when --out is -)')
         for a in p._actions:
             if a.dest == 'dataroot':
                 a.required = False
@@ -83,6 +99,34 @@ class VideoOptions(TestOptions):
         defaults = {'mc': temporal.MC_DEFAULTS['range'], 'mc_block': temporal.MC_DEFAULTS['block'], 'mc_bias': temporal.MC_DEFAULTS['bias']}
         return [a for k in defaults if k not in given for a in ('--temporal_' + k, str(defaults[k]))]
 
+    FLICKER = ('range', 'block', 'bias', 'tol', 'down')
+
+    @staticmethod
+    def _without_flicker(text):
+        """a run without --eval_flicker prints and records what it always did"""
+        return ''.join(l for l in text.splitlines(True) if not l.startswith(('eval_flicker', 'flicker_')))
+
+    def _check_flicker(self, first):
+        """the refusals of the --flicker options; returns the defaults of those not given, as arguments"""
+        from .. import flicker
+        given = {k: getattr(first, 'flicker_' + k) for k in self.FLICKER + ('csv',) if getattr(first, 'flicker_' + k) is not None}
+        if not first.eval_flicker:
+            if given:
+                raise ValueError('%s only applies with --eval_flicker' % ', '.join('--flicker_' + k for k in given))
+            return []
+        if first.video_out == '-' and 'csv' not in given:
+            raise ValueError('--eval_flicker with --out -: say where flicker.csv goes with --flicker_csv PATH')
+        values = dict(flicker.DEFAULTS, **{k: v for k, v in given.items() if k != 'csv'})
+        if values['down'] != 'auto':
+            if not values['down'].isdigit() or int(values['down']) < 1:
+                raise ValueError("--flicker_down must be auto or an integer >= 1 (got --flicker_down %s)" % values['down'])
+            values['down'] = int(values['down'])
+        try:
+            flicker.check_params(values['range'], values['block'], values['bias'], values['tol'], values['down'], '--flicker')
+        except ValueError as e:
+            raise ValueError(str(e).replace('--flicker: ', '--flicker_', 1))
+        return [a for k in self.FLICKER if k not in given for a in ('--flicker_' + k, str(flicker.DEFAULTS[k]))]
+
     def _check_temporal(self, first):
         """the refusals of the --temporal options; returns the defaults of those not given, as arguments"""
         from .. import temporal
@@ -118,7 +162,7 @@ class VideoOptions(TestOptions):
             raise ValueError('--eval_noref with --out -: say where noref.csv goes with --noref_csv PATH')
         if first.noref_csv and not first.eval_noref:
             raise ValueError('--noref_csv is where --eval_noref writes: it needs --eval_noref')
-        extra_temporal = self._check_temporal(first) + self._check_temporal_mc(first)
+        extra_temporal = self._check_temporal(first) + self._check_temporal_mc(first) + self._check_flicker(first)
         mc_on = bool(first.temporal and first.temporal_mc)
         # test.py's own checks run on what test.py would be given: frames in order, and --tile there means one image per call.  What that parse
         # prints and records is held back, corrected to the batch size this run really uses, and recorded in a file of its own: opt.txt stays
@@ -134,9 +178,12 @@ class VideoOptions(TestOptions):
         opt.batchSize = first.batchSize
         if opt.temporal and opt.temporal_down != 'auto':
             opt.temporal_down = int(opt.temporal_down)
+        if opt.eval_flicker and opt.flicker_down != 'auto':
+            opt.flicker_down = int(opt.flicker_down)
         text = held.getvalue().replace('\nbatchSize: 1\n', '\nbatchSize: %d\n' % opt.batchSize) if first.tile else held.getvalue()
         text = text if first.temporal else self._without_temporal(text)
         text = text if mc_on else self._without_temporal_mc(text)
+        text = text if first.eval_flicker else self._without_flicker(text)
         sys.stdout.write(text)
         sys.stdout.flush()
         if opt.dist_rank == 0:
@@ -144,6 +191,7 @@ class VideoOptions(TestOptions):
                 recorded = open(opt_txt).read()
                 recorded = recorded if first.temporal else self._without_temporal(recorded)
                 recorded = recorded if mc_on else self._without_temporal_mc(recorded)
+                recorded = recorded if first.eval_flicker else self._without_flicker(recorded)
                 if before is None:
                     os.remove(opt_txt)
                 else:
@@ -155,4 +203,6 @@ class VideoOptions(TestOptions):
                 print('note: could not record the options (%s)' % e)
         if opt.eval_noref and not opt.noref_csv:
             opt.noref_csv = os.path.join(os.path.dirname(os.path.abspath(opt.video_out)), 'noref.csv')
+        if opt.eval_flicker and not opt.flicker_csv:
+            opt.flicker_csv = os.path.join(os.path.dirname(os.path.abspath(opt.video_out)), 'flicker.csv')
         return opt

@@ -342,6 +342,15 @@ def run(opt, log=print):
             log("video: motion compensation within +-%d pixels, blocks of %d x %d, bias %d / 16 levels per pixel"
                 % (stabiliser.mc_range, stabiliser.mc_block, stabiliser.mc_block, stabiliser.mc_bias))
 
+    scorer, flicker_rows = None, []
+    if getattr(opt, "eval_flicker", False):
+        from . import flicker
+        scorer = flicker.Scorer(opt.flicker_range, opt.flicker_block, opt.flicker_bias, opt.flicker_tol, opt.flicker_down)
+        seconds["flicker"] = 0.0
+        S, h, w = scorer.working_size(H, W)
+        log("video: flicker along the motion at %d x %d (1/%d), search within +-%d pixels, blocks of %d x %d, bias %d / 16, tolerance %d levels"
+            % (w, h, S, scorer.range, scorer.block, scorer.block, scorer.bias, scorer.tol))
+
     def through_model(x, first):
         """the model's own batch route, the one test.py takes (the half guard included where test.py applies it)"""
         model.set_input({"B": x, "B_paths": ["frame_%06d" % (first + k) for k in range(x.shape[0])]})
@@ -372,8 +381,15 @@ def run(opt, log=print):
                 parts.append(torch.stack([o[2] for o in outs]))
             y = parts[0] if len(parts) == 1 else torch.cat(parts)
         y = y.contiguous()
+        y_net = y
         if stabiliser is not None:
             y = stabiliser.step(x, y)         # all three routes; --eval_noref scores, and the stream carries, the stabilised bytes
+        if scorer is not None:
+            t1 = time.perf_counter()
+            rows = scorer.step(x, y_net, y)   # the network's bytes and the bytes that leave, over the same pixels
+            for j, row in enumerate(rows):    # every frame of the batch but the very first of the stream
+                flicker_rows.append(("frame_%06d" % (s.first + n - len(rows) + j), row))
+            seconds["flicker"] += time.perf_counter() - t1
         if opt.eval_noref:
             t1 = time.perf_counter()
             for k, row in enumerate(metrics.noref(x, y, opt.noref_radius)):
@@ -397,6 +413,11 @@ def run(opt, log=print):
             f.write(metrics.format_noref_csv(noref_rows))
         log(metrics.noref_summary_line(noref_rows))
         log("noref: wrote %s" % opt.noref_csv)
+    if scorer is not None:
+        with open(opt.flicker_csv, "w") as f:
+            f.write(flicker.format_csv(flicker_rows))
+        log(flicker.summary_line([r for _, r in flicker_rows]))
+        log("flicker: wrote %s" % opt.flicker_csv)
     log("video: route %s, %d frames per batch, %d buffers; main-thread seconds %s" % (route, B, opt.video_buffers, {k: round(v, 3) for k, v in seconds.items()}))
     log("video: %d frames in %.2f s = %.1f frames/s stream to stream" % (frames, total, frames / max(total, 1e-9)))
     if model.redo_paths:
