@@ -63,135 +63,131 @@ class ChainArgsC(ctypes.Structure):
                [("sync_ws", c_void_p), ("sync_ws_bytes", c_size_t)]
 
 
-# every symbol include/cfen_hip.h declares: (restype, argtypes)
-_I = c_int
-_P = c_void_p
-SIGNATURES = {
-    "cfen_abi_version": (_I, []),
-    "cfen_last_error": (c_char_p, []),
-    "cfen_tune": (_I, [c_char_p, _I]),
-    "cfen_tune_query": (_I, [c_char_p, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
-    "cfen_tune_key": (c_char_p, [_I]),
-    "cfen_net_create": (_I, [ctypes.POINTER(_P), ctypes.POINTER(NetConfigC)]),
-    "cfen_net_destroy": (None, [_P]),
-    "cfen_net_workspace_bytes": (c_size_t, [_P]),
-    "cfen_net_set_param": (_I, [_P, c_char_p, _P, c_size_t]),
-    "cfen_net_missing_params": (_I, [_P, c_char_p, c_size_t]),
-    "cfen_net_actnorm_pending": (_I, [_P, c_char_p, _P, _P, _P]),
-    "cfen_net_actnorm_pending_count": (_I, [_P]),
-    "cfen_net_set_input_u8": (_I, [_P, _I]),
-    "cfen_net_set_output_u8": (_I, [_P, _I]),
-    "cfen_net_set_output_f16": (_I, [_P, _I]),
-    "cfen_net_forward": (_I, [_P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "cfen_net_graph_capture": (_I, [_P, _P, _P, _P, _P, _P, c_size_t, ctypes.POINTER(ctypes.c_int32)]),
-    "cfen_net_graph_launch": (_I, [_P, ctypes.c_int32, _P]),
-    "cfen_net_profile": (_I, [_P, _P, _P, _P, _P, _P, c_size_t, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                              ctypes.POINTER(ctypes.c_int32), _I]),
-    "cfen_net_profile_entry": (_I, [_P, _I, ctypes.POINTER(c_char_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
-                                    ctypes.POINTER(ctypes.c_double)]),
-    "cfen_net_profile_entry_kernel": (_I, [_P, _I, ctypes.POINTER(c_char_p), ctypes.POINTER(ctypes.c_double)]),
-    "cfen_net_stage": (_I, [_P, c_char_p, ctypes.POINTER(_P)] + [ctypes.POINTER(ctypes.c_int32)] * 4),
-    "cfen_net_flops_per_image": (ctypes.c_double, [_P]),
-    "cfen_net_chain_error_words": (_I, [_P, ctypes.POINTER(_P), _I]),
-    "cfen_gemm_nt": (_I, [_I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
-    "cfen_gemm_ln": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P]),
-    "cfen_gemm_splitk": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, c_size_t, _P]),
-    "cfen_head_conv5": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfen_gemm_chain": (_I, [_I, ctypes.POINTER(ChainArgsC), _I, _P]),
-    "cfen_embed_gather": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P]),
-    "cfen_u8hwc_to_nhwc": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
-    "cfen_tensor2im_u8": (_I, [_P, _P, _I, _I, _I, _P]),
-    "cfen_tile_gather": (_I, [_I, _P, _P] + [_I] * 7 + [_P]),
-    "cfen_tile_blend": (_I, [_I, _P] + [_I] * 8 + [_P, _P, _P, _P]),
-    "cfen_x8_expand": (_I, [_I, _P, _P, _I, _I, _I, _P]),
-    "cfen_x8_merge": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "cfen_image_metrics_bytes": (c_size_t, [_I] * 4),
-    "cfen_image_metrics": (_I, [_I, _P, _P] + [_I] * 4 + [c_float, c_float, _P, _P, _P]),
-    "cfen_image_msssim_bytes": (c_size_t, [_I] * 4),
-    "cfen_image_msssim": (_I, [_I, _P, _P] + [_I] * 4 + [c_float, c_float, _P, _P, _P]),
-    "cfen_png_workspace_bytes": (c_size_t, [_I] * 3 + [ctypes.POINTER(c_size_t)] * 2),
-    "cfen_png_deflate": (_I, [_P] + [_I] * 3 + [_P, _I, _P, _P, _P, _P]),
-    "cfen_embed_qkv": (_I, [_I, ctypes.POINTER(EmbedQkvArgsC), _P]),
-    "cfen_embed_qkv_stream": (_I, [_I, ctypes.POINTER(EmbedQkvArgsC), _P]),
-    "cfen_layernorm": (_I, [_I, _P, _P, _P, _P, _I, _I, c_float, _P]),
-    "cfen_attention": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
-    "cfen_attention_head_major": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
-    "cfen_mlp_block": (_I, [_I, ctypes.POINTER(MlpArgsC), _P]),
-    "cfen_mlp_stream_block": (_I, [_I, ctypes.POINTER(MlpStreamArgsC), _P]),
-    "cfen_lvit_window": (_I, [_I, ctypes.POINTER(LvitArgsC), _P]),
-    "cfen_patchify": (_I, [_I, _P, _P] + [_I] * 8 + [_P]),
-    "cfen_unpatchify": (_I, [_I, _P, _P] + [_I] * 7 + [_P]),
-    "cfen_upsample4": (_I, [_I, _P, _P] + [_I] * 6 + [_P]),
-    "cfen_nchw_to_nhwc": (_I, [_I, _P, _P] + [_I] * 5 + [_P]),
-    "cfen_conv2d": (_I, [_I, ctypes.POINTER(ConvArgsC), _P]),
-    "cfen_stats_workspace": (c_size_t, [_I, _I]),
-    "cfen_instnorm_relu": (_I, [_I, _P, _P, _I, _I, _I, _I, c_float, _P]),
-    "cfen_cfsm2g": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfen_deform_conv_columns_bytes": (c_size_t, [_I] * 9),
-    "cfen_deform_conv_forward": (_I, [_I, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
-    "cfen_modulated_deform_conv_forward": (_I, [_I, _P, _P, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
-    "cfen_deform_conv_forward_nhwc": (_I, [_I, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
-    "cfen_modulated_deform_conv_forward_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
-    "cfen_deform_conv_backward_bytes": (c_size_t, [_I] * 10),
-    "cfen_deform_conv_backward_set_lds": (_I, [_I]),
-    "cfen_deform_conv_backward_input": (_I, [_I, _P, _P, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
-    "cfen_deform_conv_backward_parameters": (_I, [_I, _P, _P, _P, _P] + [_I] * 15 + [c_float, _I, _P, c_size_t, _P]),
-    "cfen_modulated_deform_conv_backward": (_I, [_I] + [_P] * 11 + [_I] * 16 + [_P, c_size_t, _P]),
-}
-
-# every symbol include/cfen_resample.h declares: an extension with a header of its own; include/cfen_hip.h, SIGNATURES and cfen_abi_version() do not change
-EXTENSION_SIGNATURES = {
-    "cfen_resample_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
-}
-
-# every symbol include/cfen_guided.h declares: a second extension with a header of its own, bound beside the other two
-GUIDED_SIGNATURES = {
-    "cfen_guided_coef_u8": (_I, [_P, _P, _I, _I, _I, _I, c_float, _P, _P, _P]),
-    "cfen_guided_apply_u8": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
-}
-
-# every symbol include/cfen_colordiff.h declares: the CIEDE2000 extension, bound beside the other three
-COLORDIFF_SIGNATURES = {
-    "cfen_ciede2000_bytes": (c_size_t, [_I, _I, _I]),
-    "cfen_ciede2000_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
-}
-
-# every symbol include/cfen_noref.h declares: the no-reference statistics extension, bound beside the other four
-NOREF_SIGNATURES = {
-    "cfen_noref_bytes": (c_size_t, [_I, _I, _I, _I]),
-    "cfen_noref_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-}
-
-
 class YuvTableC(ctypes.Structure):
     """cfen_yuv_table of include/cfen_yuv.h, passed by value: 9 coefficients in units of 2^-14, the luma offset, 6 reserved zeros"""
     _fields_ = [("coef", ctypes.c_int32 * 9), ("luma_offset", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
 
 
-# every symbol include/cfen_yuv.h declares: the YCbCr <-> RGB extension, bound beside the other five
-YUV_SIGNATURES = {
-    "cfen_yuv_frame_bytes": (c_size_t, [_I, _I, _I]),
-    "cfen_yuv_to_rgb_u8": (_I, [_P, c_size_t, _I, _I, _I, _I, YuvTableC, _P, _P]),
-    "cfen_rgb_to_yuv_u8": (_I, [_P, _I, _I, _I, _I, YuvTableC, _P, c_size_t, _P]),
+_I = c_int
+_P = c_void_p
+# {header under include/: {symbol it declares: (restype, argtypes)}}.  cfen_hip.h is the frozen core (cfen_abi_version() == 1); every other header is an
+# extension that leaves it unchanged.  A new header is one more entry here: load() binds whatever the table holds.
+HEADERS = {
+    # the frozen core
+    "cfen_hip.h": {
+        "cfen_abi_version": (_I, []),
+        "cfen_last_error": (c_char_p, []),
+        "cfen_tune": (_I, [c_char_p, _I]),
+        "cfen_tune_query": (_I, [c_char_p, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+        "cfen_tune_key": (c_char_p, [_I]),
+        "cfen_net_create": (_I, [ctypes.POINTER(_P), ctypes.POINTER(NetConfigC)]),
+        "cfen_net_destroy": (None, [_P]),
+        "cfen_net_workspace_bytes": (c_size_t, [_P]),
+        "cfen_net_set_param": (_I, [_P, c_char_p, _P, c_size_t]),
+        "cfen_net_missing_params": (_I, [_P, c_char_p, c_size_t]),
+        "cfen_net_actnorm_pending": (_I, [_P, c_char_p, _P, _P, _P]),
+        "cfen_net_actnorm_pending_count": (_I, [_P]),
+        "cfen_net_set_input_u8": (_I, [_P, _I]),
+        "cfen_net_set_output_u8": (_I, [_P, _I]),
+        "cfen_net_set_output_f16": (_I, [_P, _I]),
+        "cfen_net_forward": (_I, [_P, _P, _P, _P, _P, _P, c_size_t, _P]),
+        "cfen_net_graph_capture": (_I, [_P, _P, _P, _P, _P, _P, c_size_t, ctypes.POINTER(ctypes.c_int32)]),
+        "cfen_net_graph_launch": (_I, [_P, ctypes.c_int32, _P]),
+        "cfen_net_profile": (_I, [_P, _P, _P, _P, _P, _P, c_size_t, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                  ctypes.POINTER(ctypes.c_int32), _I]),
+        "cfen_net_profile_entry": (_I, [_P, _I, ctypes.POINTER(c_char_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_double)]),
+        "cfen_net_profile_entry_kernel": (_I, [_P, _I, ctypes.POINTER(c_char_p), ctypes.POINTER(ctypes.c_double)]),
+        "cfen_net_stage": (_I, [_P, c_char_p, ctypes.POINTER(_P)] + [ctypes.POINTER(ctypes.c_int32)] * 4),
+        "cfen_net_flops_per_image": (ctypes.c_double, [_P]),
+        "cfen_net_chain_error_words": (_I, [_P, ctypes.POINTER(_P), _I]),
+        "cfen_gemm_nt": (_I, [_I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+        "cfen_gemm_ln": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P]),
+        "cfen_gemm_splitk": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, c_size_t, _P]),
+        "cfen_head_conv5": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+        "cfen_gemm_chain": (_I, [_I, ctypes.POINTER(ChainArgsC), _I, _P]),
+        "cfen_embed_gather": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P]),
+        "cfen_u8hwc_to_nhwc": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
+        "cfen_tensor2im_u8": (_I, [_P, _P, _I, _I, _I, _P]),
+        "cfen_tile_gather": (_I, [_I, _P, _P] + [_I] * 7 + [_P]),
+        "cfen_tile_blend": (_I, [_I, _P] + [_I] * 8 + [_P, _P, _P, _P]),
+        "cfen_x8_expand": (_I, [_I, _P, _P, _I, _I, _I, _P]),
+        "cfen_x8_merge": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),
+        "cfen_image_metrics_bytes": (c_size_t, [_I] * 4),
+        "cfen_image_metrics": (_I, [_I, _P, _P] + [_I] * 4 + [c_float, c_float, _P, _P, _P]),
+        "cfen_image_msssim_bytes": (c_size_t, [_I] * 4),
+        "cfen_image_msssim": (_I, [_I, _P, _P] + [_I] * 4 + [c_float, c_float, _P, _P, _P]),
+        "cfen_png_workspace_bytes": (c_size_t, [_I] * 3 + [ctypes.POINTER(c_size_t)] * 2),
+        "cfen_png_deflate": (_I, [_P] + [_I] * 3 + [_P, _I, _P, _P, _P, _P]),
+        "cfen_embed_qkv": (_I, [_I, ctypes.POINTER(EmbedQkvArgsC), _P]),
+        "cfen_embed_qkv_stream": (_I, [_I, ctypes.POINTER(EmbedQkvArgsC), _P]),
+        "cfen_layernorm": (_I, [_I, _P, _P, _P, _P, _I, _I, c_float, _P]),
+        "cfen_attention": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
+        "cfen_attention_head_major": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
+        "cfen_mlp_block": (_I, [_I, ctypes.POINTER(MlpArgsC), _P]),
+        "cfen_mlp_stream_block": (_I, [_I, ctypes.POINTER(MlpStreamArgsC), _P]),
+        "cfen_lvit_window": (_I, [_I, ctypes.POINTER(LvitArgsC), _P]),
+        "cfen_patchify": (_I, [_I, _P, _P] + [_I] * 8 + [_P]),
+        "cfen_unpatchify": (_I, [_I, _P, _P] + [_I] * 7 + [_P]),
+        "cfen_upsample4": (_I, [_I, _P, _P] + [_I] * 6 + [_P]),
+        "cfen_nchw_to_nhwc": (_I, [_I, _P, _P] + [_I] * 5 + [_P]),
+        "cfen_conv2d": (_I, [_I, ctypes.POINTER(ConvArgsC), _P]),
+        "cfen_stats_workspace": (c_size_t, [_I, _I]),
+        "cfen_instnorm_relu": (_I, [_I, _P, _P, _I, _I, _I, _I, c_float, _P]),
+        "cfen_cfsm2g": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+        "cfen_deform_conv_columns_bytes": (c_size_t, [_I] * 9),
+        "cfen_deform_conv_forward": (_I, [_I, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
+        "cfen_modulated_deform_conv_forward": (_I, [_I, _P, _P, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
+        "cfen_deform_conv_forward_nhwc": (_I, [_I, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
+        "cfen_modulated_deform_conv_forward_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
+        "cfen_deform_conv_backward_bytes": (c_size_t, [_I] * 10),
+        "cfen_deform_conv_backward_set_lds": (_I, [_I]),
+        "cfen_deform_conv_backward_input": (_I, [_I, _P, _P, _P, _P, _P, _P] + [_I] * 16 + [_P, c_size_t, _P]),
+        "cfen_deform_conv_backward_parameters": (_I, [_I, _P, _P, _P, _P] + [_I] * 15 + [c_float, _I, _P, c_size_t, _P]),
+        "cfen_modulated_deform_conv_backward": (_I, [_I] + [_P] * 11 + [_I] * 16 + [_P, c_size_t, _P]),
+    },
+    # PIL-exact uint8 resampling
+    "cfen_resample.h": {
+        "cfen_resample_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
+    },
+    # guided upsampling
+    "cfen_guided.h": {
+        "cfen_guided_coef_u8": (_I, [_P, _P, _I, _I, _I, _I, c_float, _P, _P, _P]),
+        "cfen_guided_apply_u8": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
+    },
+    # CIEDE2000
+    "cfen_colordiff.h": {
+        "cfen_ciede2000_bytes": (c_size_t, [_I, _I, _I]),
+        "cfen_ciede2000_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    },
+    # no-reference statistics
+    "cfen_noref.h": {
+        "cfen_noref_bytes": (c_size_t, [_I, _I, _I, _I]),
+        "cfen_noref_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    },
+    # YCbCr <-> RGB
+    "cfen_yuv.h": {
+        "cfen_yuv_frame_bytes": (c_size_t, [_I, _I, _I]),
+        "cfen_yuv_to_rgb_u8": (_I, [_P, c_size_t, _I, _I, _I, _I, YuvTableC, _P, _P]),
+        "cfen_rgb_to_yuv_u8": (_I, [_P, _I, _I, _I, _I, YuvTableC, _P, c_size_t, _P]),
+    },
+    # temporal stabilisation
+    "cfen_temporal.h": {
+        "cfen_temporal_blend": (_I, [_P, _P, _P, _I, _I, _I, _I, c_float, c_float, _I, _P, _P, _P]),
+        "cfen_temporal_apply_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    },
+    # motion compensation
+    "cfen_motion.h": {
+        "cfen_motion_search_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+        "cfen_motion_warp": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    },
+    # flicker along the motion
+    "cfen_flicker.h": {
+        "cfen_flicker_bytes": (c_size_t, [_I, _I, _I]),
+        "cfen_flicker_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    },
 }
-
-# every symbol include/cfen_temporal.h declares: the temporal stabilisation extension, bound beside the other six
-TEMPORAL_SIGNATURES = {
-    "cfen_temporal_blend": (_I, [_P, _P, _P, _I, _I, _I, _I, c_float, c_float, _I, _P, _P, _P]),
-    "cfen_temporal_apply_u8": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
-}
-
-# every symbol include/cfen_motion.h declares: the motion compensation extension, bound beside the other seven
-MOTION_SIGNATURES = {
-    "cfen_motion_search_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "cfen_motion_warp": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
-}
-
-# every symbol include/cfen_flicker.h declares: the flicker-along-the-motion extension, bound beside the other eight
-FLICKER_SIGNATURES = {
-    "cfen_flicker_bytes": (c_size_t, [_I, _I, _I]),
-    "cfen_flicker_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
-}
+SIGNATURES = HEADERS["cfen_hip.h"]          # the core table, by the name the frozen ABI's tests and documents use
 
 _lib = None
 
@@ -205,12 +201,11 @@ def load():
         raise ImportError("libcfen_hip.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950) -- there is no CPU/PyTorch fallback for the HIP path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(GUIDED_SIGNATURES.items()) + \
-            list(COLORDIFF_SIGNATURES.items()) + list(NOREF_SIGNATURES.items()) + list(YUV_SIGNATURES.items()) + list(TEMPORAL_SIGNATURES.items()) + \
-            list(MOTION_SIGNATURES.items()) + list(FLICKER_SIGNATURES.items()):
-        fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
+    for table in HEADERS.values():
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

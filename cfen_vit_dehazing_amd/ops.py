@@ -7,6 +7,7 @@ is no PyTorch fallback.
 import contextlib
 import ctypes
 import functools
+import math
 
 import torch
 
@@ -30,6 +31,64 @@ def _out(out, shape, dtype, device, what, zero=False):
     if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
         raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shape, device))
     return out
+
+
+def _tensor_arg(what, name, t, shape, dtype, like=None):
+    """argument `name` of operator `what`: ValueError unless `t` is a contiguous CUDA tensor of `dtype` whose sizes are `shape` (None: any size >= 1,
+    written B, H, W in the message), on the device of the tensor `like` if one is given"""
+    if not isinstance(t, torch.Tensor) or t.dim() != len(shape) or t.dtype != dtype or (like is not None and t.device != like.device) or \
+            any(n < 1 if s is None else n != s for n, s in zip(t.shape, shape)):
+        want = ",".join("BHW"[i + 4 - len(shape)] if s is None else str(s) for i, s in enumerate(shape))
+        raise ValueError("%s needs %s as a contiguous (%s) %s tensor%s, got %s" % (
+            what, name, want, str(dtype)[len("torch."):], "" if like is None else " on %s" % like.device,
+            "%s %s on %s" % (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
+    _cuda(t)
+
+
+def _rgb_batch(what, **images):
+    """each of `images` (name=tensor) is a contiguous (B,H,W,3) uint8 CUDA tensor"""
+    for name, t in images.items():
+        _tensor_arg(what, name, t, (None, None, None, 3), torch.uint8)
+
+
+def _rgb_pair(what, **images):
+    """the two images of a comparison: _rgb_batch, and of one shape on one device"""
+    _rgb_batch(what, **images)
+    (na, a), (nb, b) = images.items()
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("%s: %s %s and %s %s differ in shape or device" % (what, na, tuple(a.shape), nb, tuple(b.shape)))
+
+
+def _int_arg(what, name, v, lo, hi, choices=None):
+    """`v` (a Python or numpy scalar, a 0-d tensor) as an int, if it is a whole number in lo .. hi -- or one of `choices`, if given"""
+    try:
+        i = int(v)
+    except (TypeError, ValueError, OverflowError):
+        i = None
+    if i is None or i != v or not (lo <= i <= hi if choices is None else i in choices):
+        rule = "an integer in %d .. %d" % (lo, hi) if choices is None else "%s or %d" % (", ".join(str(c) for c in choices[:-1]), choices[-1])
+        raise ValueError("%s: %s must be %s, got %r" % (what, name, rule, v))
+    return i
+
+
+def _float_arg(what, name, v, test, rule):
+    """`v` as a float, if test(float(v)) holds; `rule` says in the message what `test` asks for"""
+    try:
+        f = float(v)
+    except (TypeError, ValueError, OverflowError):
+        f = None
+    if f is None or not test(f):
+        raise ValueError("%s: %s must be %s, got %r" % (what, name, rule, v))
+    return f
+
+
+def _scratch_for(what, bytes_fn, dims, device, limits=None):
+    """a kernel's scratch of doubles, of the size the library's bytes_fn(*dims) asks for (it goes back to torch's allocator on the stream it was used
+    on).  The library answers 0 for sizes its entry point refuses: ValueError with `limits`, or without it left to the entry point's own message"""
+    nbytes = bytes_fn(*dims)
+    if nbytes == 0 and limits is not None:
+        raise ValueError("%s: sizes %s are outside the limits (%s)" % (what, tuple(dims), limits))
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
 
 
 def tune(key, value):
@@ -488,12 +547,10 @@ def resample_u8(images_u8, size, filter="bicubic", out=None):
     horizontal pass runs if W2 != W into a uint8 intermediate, the vertical pass if H2 != H; with neither the result is a copy.  out: the caller's
     (B,H2,W2,3) uint8 tensor, which may be a lane of a larger slab (no alignment is assumed)."""
     from . import resample
-    _cuda(images_u8)
-    if images_u8.dim() != 4 or images_u8.shape[3] != 3 or images_u8.dtype != torch.uint8:
-        raise ValueError("resample_u8 needs a contiguous (B,H,W,3) uint8 tensor, got %s %s" % (tuple(images_u8.shape), images_u8.dtype))
+    _rgb_batch("resample_u8", images_u8=images_u8)
     B, H, W, _ = images_u8.shape
     H2, W2 = (int(s) for s in size)
-    if min(B, H, W, H2, W2) < 1:
+    if min(H2, W2) < 1:
         raise ValueError("resample_u8: empty image or target, %s -> %s" % (tuple(images_u8.shape), (H2, W2)))
     dev = images_u8.device
     out = _out(out, (B, H2, W2, 3), torch.uint8, dev, "resample_u8")
@@ -505,34 +562,15 @@ def resample_u8(images_u8, size, filter="bicubic", out=None):
     return out      # (tmp goes back to torch's allocator on the stream it was used on)
 
 
-def _guided_images(what, **images):
-    for name, t in images.items():
-        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8 or min(t.shape) < 1:
-            raise ValueError("%s needs %s as a contiguous (B,H,W,3) uint8 tensor, got %s" % (
-                what, name, "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
-    _cuda(*images.values())
-
-
 def _guided_params(what, radius, eps):
-    import math
-    try:
-        r, e = int(radius), float(eps)          # Python and numpy scalars, 0-d tensors
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("%s: radius must be an integer in 1 .. 16 and eps a number, got radius %r, eps %r" % (what, radius, eps))
-    if r != radius or not 1 <= r <= 16:
-        raise ValueError("%s: radius must be an integer in 1 .. 16, got %r" % (what, radius))
-    if not (math.isfinite(e) and e > 0):
-        raise ValueError("%s: eps must be finite and > 0, got %r" % (what, eps))
-    return r, e * 255.0 * 255.0          # eps is in squared units of the [0, 1] scale; the kernels work on bytes
+    radius = _int_arg(what, "radius", radius, 1, 16)
+    eps = _float_arg(what, "eps", eps, lambda e: math.isfinite(e) and e > 0, "finite and > 0")
+    return radius, eps * 255.0 * 255.0          # eps is in squared units of the [0, 1] scale; the kernels work on bytes
 
 
 def _field(what, name, t, guide_hi):
     """the coefficient (or delta) field an apply kernel upsamples to the size of guide_hi"""
-    if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[3] != 6 or t.dtype != torch.float32 or min(t.shape) < 1 or \
-            t.shape[0] != guide_hi.shape[0] or t.device != guide_hi.device:
-        raise ValueError("%s needs %s as a contiguous (B,h,w,6) float32 tensor for the %d images of guide_hi, got %s"
-                         % (what, name, guide_hi.shape[0], "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
-    _cuda(t)
+    _tensor_arg(what, name, t, (guide_hi.shape[0], None, None, 6), torch.float32, like=guide_hi)
 
 
 def guided_coef_u8(guide_lo, src_lo, radius=2, eps=1e-4, out=None):
@@ -540,9 +578,7 @@ def guided_coef_u8(guide_lo, src_lo, radius=2, eps=1e-4, out=None):
     and channel over a (2 radius + 1)^2 window: (B,h,w,6) float32 = [abar_R, abar_G, abar_B, bbar_R, bbar_G, bbar_B] on the 0..255 scale.
     guide_lo, src_lo: contiguous (B,h,w,3) uint8 CUDA tensors; eps regularises the variance, in squared units of the [0, 1] scale.  out: the
     caller's (B,h,w,6) float32 tensor."""
-    _guided_images("guided_coef_u8", guide_lo=guide_lo, src_lo=src_lo)
-    if guide_lo.shape != src_lo.shape or guide_lo.device != src_lo.device:
-        raise ValueError("guided_coef_u8: guide_lo %s and src_lo %s differ in shape or device" % (tuple(guide_lo.shape), tuple(src_lo.shape)))
+    _rgb_pair("guided_coef_u8", guide_lo=guide_lo, src_lo=src_lo)
     radius, eps255 = _guided_params("guided_coef_u8", radius, eps)
     B, h, w, _ = guide_lo.shape
     dev = guide_lo.device
@@ -556,7 +592,7 @@ def guided_apply_u8(coef, guide_hi, out=None):
     """cfen_guided_apply_u8 (include/cfen_guided.h): coef (B,h,w,6) float32 of guided_coef_u8, upsampled bilinearly (half-pixel centres, edge clamp)
     to the size of guide_hi (B,H,W,3) uint8 and applied to it: (B,H,W,3) uint8 = clamp(floor(Abar * guide_hi + Bbar + 0.5), 0, 255).  out: the
     caller's (B,H,W,3) uint8 tensor, which may be a lane of a larger slab (no alignment is assumed)."""
-    _guided_images("guided_apply_u8", guide_hi=guide_hi)
+    _rgb_batch("guided_apply_u8", guide_hi=guide_hi)
     _field("guided_apply_u8", "coef", coef, guide_hi)
     B, H, W, _ = guide_hi.shape
     out = _out(out, (B, H, W, 3), torch.uint8, guide_hi.device, "guided_apply_u8")
@@ -568,26 +604,10 @@ def guided_upsample_u8(guide_hi, guide_lo, src_lo, radius=2, eps=1e-4, out=None)
     """Guided upsampling (He & Sun, "Fast Guided Filter") of src_lo (B,h,w,3) uint8 to the size of guide_hi (B,H,W,3) uint8, where guide_lo
     (B,h,w,3) is the low-resolution guide src_lo was computed from: guided_apply_u8(guided_coef_u8(guide_lo, src_lo, radius, eps), guide_hi).
     Three launches."""
-    _guided_images("guided_upsample_u8", guide_hi=guide_hi, guide_lo=guide_lo, src_lo=src_lo)
+    _rgb_batch("guided_upsample_u8", guide_hi=guide_hi, guide_lo=guide_lo, src_lo=src_lo)
     if guide_hi.shape[0] != guide_lo.shape[0]:
         raise ValueError("guided_upsample_u8: guide_hi %s and guide_lo %s differ in batch" % (tuple(guide_hi.shape), tuple(guide_lo.shape)))
     return guided_apply_u8(guided_coef_u8(guide_lo, src_lo, radius, eps), guide_hi, out=out)
-
-
-def _temporal_params(what, radius, motion, strength):
-    import math
-    try:
-        r, m, s = int(radius), float(motion), float(strength)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("%s: radius must be an integer in 1 .. 16, motion and strength numbers, got radius %r, motion %r, strength %r"
-                         % (what, radius, motion, strength))
-    if r != radius or not 1 <= r <= 16:
-        raise ValueError("%s: radius must be an integer in 1 .. 16, got %r" % (what, radius))
-    if not (math.isfinite(m) and m > 0):
-        raise ValueError("%s: motion must be finite and > 0, got %r" % (what, motion))
-    if not 0 <= s < 1:
-        raise ValueError("%s: strength must be in [0, 1), got %r" % (what, strength))
-    return r, m, s
 
 
 def temporal_blend(guide, prev_guide, coef, state, radius=2, motion=8.0, strength=0.8, have_state=True, out=None):
@@ -596,22 +616,17 @@ def temporal_blend(guide, prev_guide, coef, state, radius=2, motion=8.0, strengt
     S_t - c_t and updates state (h,w,6) float32 in place to S of the last frame.  prev_guide (h,w,3) uint8 is the frame before guide[0]; it is only
     read.  have_state False: guide[0] is the first frame of a stream, prev_guide (may be None) and what state holds are not looked at.  out: the
     caller's (B,h,w,6) float32 tensor."""
-    _guided_images("temporal_blend", guide=guide)
+    _rgb_batch("temporal_blend", guide=guide)
     B, h, w, _ = guide.shape
     dev = guide.device
-    if not isinstance(coef, torch.Tensor) or tuple(coef.shape) != (B, h, w, 6) or coef.dtype != torch.float32 or coef.device != dev:
-        raise ValueError("temporal_blend needs coef as a contiguous (%d,%d,%d,6) float32 tensor on the device of guide, got %s"
-                         % (B, h, w, "%s %s" % (tuple(coef.shape), coef.dtype) if isinstance(coef, torch.Tensor) else type(coef).__name__))
-    if not isinstance(state, torch.Tensor) or tuple(state.shape) != (h, w, 6) or state.dtype != torch.float32 or state.device != dev:
-        raise ValueError("temporal_blend needs state as a contiguous (%d,%d,6) float32 tensor on the device of guide, got %s"
-                         % (h, w, "%s %s" % (tuple(state.shape), state.dtype) if isinstance(state, torch.Tensor) else type(state).__name__))
+    _tensor_arg("temporal_blend", "coef", coef, (B, h, w, 6), torch.float32, like=guide)
+    _tensor_arg("temporal_blend", "state", state, (h, w, 6), torch.float32, like=guide)
     have_state = bool(have_state)
-    if have_state and (not isinstance(prev_guide, torch.Tensor) or tuple(prev_guide.shape) != (h, w, 3) or prev_guide.dtype != torch.uint8 or
-                       prev_guide.device != dev):
-        raise ValueError("temporal_blend with have_state needs prev_guide as a contiguous (%d,%d,3) uint8 tensor on the device of guide, got %s"
-                         % (h, w, "%s %s" % (tuple(prev_guide.shape), prev_guide.dtype) if isinstance(prev_guide, torch.Tensor) else type(prev_guide).__name__))
-    _cuda(coef, state, prev_guide if have_state else None)
-    radius, motion, strength = _temporal_params("temporal_blend", radius, motion, strength)
+    if have_state:
+        _tensor_arg("temporal_blend with have_state", "prev_guide", prev_guide, (h, w, 3), torch.uint8, like=guide)
+    radius = _int_arg("temporal_blend", "radius", radius, 1, 16)
+    motion = _float_arg("temporal_blend", "motion", motion, lambda m: math.isfinite(m) and m > 0, "finite and > 0")
+    strength = _float_arg("temporal_blend", "strength", strength, lambda s: 0 <= s < 1, "in [0, 1)")
     out = _out(out, (B, h, w, 6), torch.float32, dev, "temporal_blend")
     check(_lib.load().cfen_temporal_blend(ptr(guide), ptr(prev_guide if have_state else None), ptr(coef), B, h, w, radius, motion, strength,
                                           int(have_state), ptr(state), ptr(out), current_stream()), "temporal_blend")
@@ -623,9 +638,7 @@ def temporal_apply_u8(delta, guide_hi, src_hi, out=None):
     to the size of guide_hi and src_hi (B,H,W,3) uint8 -- the hazy and the dehazed frames -- and applied as a correction of src_hi:
     (B,H,W,3) uint8 = clamp(floor(src_hi + DA * guide_hi + DB + 0.5), 0, 255).  out: the caller's (B,H,W,3) uint8 tensor, which may be a lane of a
     larger slab (no alignment is assumed)."""
-    _guided_images("temporal_apply_u8", guide_hi=guide_hi, src_hi=src_hi)
-    if guide_hi.shape != src_hi.shape or guide_hi.device != src_hi.device:
-        raise ValueError("temporal_apply_u8: guide_hi %s and src_hi %s differ in shape or device" % (tuple(guide_hi.shape), tuple(src_hi.shape)))
+    _rgb_pair("temporal_apply_u8", guide_hi=guide_hi, src_hi=src_hi)
     _field("temporal_apply_u8", "delta", delta, guide_hi)
     B, H, W, _ = guide_hi.shape
     out = _out(out, (B, H, W, 3), torch.uint8, guide_hi.device, "temporal_apply_u8")
@@ -635,13 +648,7 @@ def temporal_apply_u8(delta, guide_hi, src_hi, out=None):
 
 
 def _motion_block(what, block):
-    try:
-        b = int(block)
-    except (TypeError, ValueError, OverflowError):
-        b = None
-    if b is None or b != block or b not in (8, 16, 32):
-        raise ValueError("%s: block must be 8, 16 or 32, got %r" % (what, block))
-    return b
+    return _int_arg(what, "block", block, 8, 32, choices=(8, 16, 32))
 
 
 def _pair(out):
@@ -657,22 +664,13 @@ def motion_search_u8(guide, prev_guide, block, range, bias, out=None):
     uint8, the displacement (dy, dx) within +-range at which the previous frame matches best (the smallest 16 SAD + bias (|dy| + |dx|) 3 n_b, ties
     to the shorter and then the lexicographically smaller vector), in one launch: returns (vec (B,bh,bw,2) int16, sad (B,bh,bw) int32, the
     winner's SAD).  prev_guide (h,w,3) uint8 is the frame before guide[0].  out: the caller's (vec, sad) pair."""
-    _guided_images("motion_search_u8", guide=guide)
+    _rgb_batch("motion_search_u8", guide=guide)
     B, h, w, _ = guide.shape
     dev = guide.device
-    if not isinstance(prev_guide, torch.Tensor) or tuple(prev_guide.shape) != (h, w, 3) or prev_guide.dtype != torch.uint8 or prev_guide.device != dev:
-        raise ValueError("motion_search_u8 needs prev_guide as a contiguous (%d,%d,3) uint8 tensor on the device of guide, got %s"
-                         % (h, w, "%s %s" % (tuple(prev_guide.shape), prev_guide.dtype) if isinstance(prev_guide, torch.Tensor) else type(prev_guide).__name__))
-    _cuda(prev_guide)
+    _tensor_arg("motion_search_u8", "prev_guide", prev_guide, (h, w, 3), torch.uint8, like=guide)
     block = _motion_block("motion_search_u8", block)
-    try:
-        r, bi = int(range), int(bias)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("motion_search_u8: range and bias must be integers, got range %r, bias %r" % (range, bias))
-    if r != range or not 1 <= r <= 16:
-        raise ValueError("motion_search_u8: range must be an integer in 1 .. 16, got %r" % (range,))
-    if bi != bias or not 0 <= bi <= 255:
-        raise ValueError("motion_search_u8: bias must be an integer in 0 .. 255, got %r" % (bias,))
+    r = _int_arg("motion_search_u8", "range", range, 1, 16)
+    bi = _int_arg("motion_search_u8", "bias", bias, 0, 255)
     bh, bw = -(-h // block), -(-w // block)
     vec, sad = _pair(out)
     vec = _out(vec, (B, bh, bw, 2), torch.int16, dev, "motion_search_u8")
@@ -686,21 +684,13 @@ def motion_warp(vec, prev_guide, state, block, out=None):
     float32 fetched, per pixel, from where its block's vector vec (bh,bw,2) int16 of motion_search_u8 points (coordinates clamped to the
     frame): returns (prev_out (h,w,3) uint8, state_out (h,w,6) float32).  A pure gather; inputs and outputs must not overlap.  out: the caller's
     (prev_out, state_out) pair."""
-    if not isinstance(prev_guide, torch.Tensor) or prev_guide.dim() != 3 or prev_guide.shape[2] != 3 or prev_guide.dtype != torch.uint8 or \
-            min(prev_guide.shape) < 1:
-        raise ValueError("motion_warp needs prev_guide as a contiguous (h,w,3) uint8 tensor, got %s"
-                         % ("%s %s" % (tuple(prev_guide.shape), prev_guide.dtype) if isinstance(prev_guide, torch.Tensor) else type(prev_guide).__name__))
+    _tensor_arg("motion_warp", "prev_guide", prev_guide, (None, None, 3), torch.uint8)
     h, w, _ = prev_guide.shape
     dev = prev_guide.device
     block = _motion_block("motion_warp", block)
     bh, bw = -(-h // block), -(-w // block)
-    if not isinstance(vec, torch.Tensor) or tuple(vec.shape) != (bh, bw, 2) or vec.dtype != torch.int16 or vec.device != dev:
-        raise ValueError("motion_warp needs vec as a contiguous (%d,%d,2) int16 tensor on the device of prev_guide, got %s"
-                         % (bh, bw, "%s %s" % (tuple(vec.shape), vec.dtype) if isinstance(vec, torch.Tensor) else type(vec).__name__))
-    if not isinstance(state, torch.Tensor) or tuple(state.shape) != (h, w, 6) or state.dtype != torch.float32 or state.device != dev:
-        raise ValueError("motion_warp needs state as a contiguous (%d,%d,6) float32 tensor on the device of prev_guide, got %s"
-                         % (h, w, "%s %s" % (tuple(state.shape), state.dtype) if isinstance(state, torch.Tensor) else type(state).__name__))
-    _cuda(vec, prev_guide, state)
+    _tensor_arg("motion_warp", "vec", vec, (bh, bw, 2), torch.int16, like=prev_guide)
+    _tensor_arg("motion_warp", "state", state, (h, w, 6), torch.float32, like=prev_guide)
     prev_out, state_out = _pair(out)
     prev_out = _out(prev_out, (h, w, 3), torch.uint8, dev, "motion_warp")
     state_out = _out(state_out, (h, w, 6), torch.float32, dev, "motion_warp")
@@ -722,16 +712,11 @@ def _image_pair(what, a, b):
     return a, b, u8, B, C, H, W
 
 
-def _f64_scratch(nbytes, device):
-    """a kernel's scratch of doubles (it goes back to torch's allocator on the stream it was used on)"""
-    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
-
-
 def _image_pair_scores(what, ncol, a, b, value_range, out):
     """cfen_<what> on the pair (a, b): the (B, ncol) float64 tensor of its results"""
     a, b, u8, B, C, H, W = _image_pair(what, a, b)
     lib = _lib.load()
-    scratch = _f64_scratch(getattr(lib, "cfen_%s_bytes" % what)(B, C, H, W), a.device)
+    scratch = _scratch_for(what, getattr(lib, "cfen_%s_bytes" % what), (B, C, H, W), a.device)      # sizes it refuses: cfen_<what>'s own error
     if out is None:
         out = torch.empty(B, ncol, dtype=torch.float64, device=a.device)
     elif tuple(out.shape) != (B, ncol) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
@@ -748,35 +733,19 @@ def flicker_u8(guide, prev_guide, tgt, prev_tgt, vec, block, tol, out=None):
     prev_tgt prev_guide.  Returns (B,8) int64: n_cov, n_match, sum_matched dI, sum_matched dF, sum_matched eF, sum_covered dF, sum_covered dI, 0;
     flicker.scores_from_sums turns them into scores.  Two launches; the same bits at every batch size and on every stream.  out: the caller's
     (B,8) int64 tensor."""
-    _guided_images("flicker_u8", guide=guide, tgt=tgt)
+    _rgb_pair("flicker_u8", guide=guide, tgt=tgt)
     B, h, w, _ = guide.shape
     dev = guide.device
-    if tgt.shape != guide.shape or tgt.device != dev:
-        raise ValueError("flicker_u8: guide %s and tgt %s differ in shape or device" % (tuple(guide.shape), tuple(tgt.shape)))
-    for name, t in (("prev_guide", prev_guide), ("prev_tgt", prev_tgt)):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (h, w, 3) or t.dtype != torch.uint8 or t.device != dev:
-            raise ValueError("flicker_u8 needs %s as a contiguous (%d,%d,3) uint8 tensor on the device of guide, got %s"
-                             % (name, h, w, "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
-    _cuda(prev_guide, prev_tgt)
+    _tensor_arg("flicker_u8", "prev_guide", prev_guide, (h, w, 3), torch.uint8, like=guide)
+    _tensor_arg("flicker_u8", "prev_tgt", prev_tgt, (h, w, 3), torch.uint8, like=guide)
     block = _motion_block("flicker_u8", block)
-    try:
-        tl = int(tol)
-    except (TypeError, ValueError, OverflowError):
-        tl = None
-    if tl is None or tl != tol or not 0 <= tl <= 255:
-        raise ValueError("flicker_u8: tol must be an integer in 0 .. 255, got %r" % (tol,))
+    tl = _int_arg("flicker_u8", "tol", tol, 0, 255)
     bh, bw = -(-h // block), -(-w // block)
     if vec is not None:
-        if not isinstance(vec, torch.Tensor) or tuple(vec.shape) != (B, bh, bw, 2) or vec.dtype != torch.int16 or vec.device != dev:
-            raise ValueError("flicker_u8 needs vec as None or a contiguous (%d,%d,%d,2) int16 tensor on the device of guide, got %s"
-                             % (B, bh, bw, "%s %s" % (tuple(vec.shape), vec.dtype) if isinstance(vec, torch.Tensor) else type(vec).__name__))
-        _cuda(vec)
+        _tensor_arg("flicker_u8", "vec", vec, (B, bh, bw, 2), torch.int16, like=guide)
     lib = _lib.load()
-    nbytes = lib.cfen_flicker_bytes(B, h, w)
-    if nbytes == 0:
-        raise ValueError("flicker_u8: %d frames of %d x %d are outside the limits (B <= 65536, h, w <= 16384, at most 2^31 - 1 tiles of 64 x 64)" % (B, h, w))
+    scratch = _scratch_for("flicker_u8", lib.cfen_flicker_bytes, (B, h, w), dev, "B <= 65536, h, w <= 16384, at most 2^31 - 1 tiles of 64 x 64")
     out = _out(out, (B, 8), torch.int64, dev, "flicker_u8")
-    scratch = _f64_scratch(nbytes, dev)
     check(lib.cfen_flicker_u8(ptr(guide), ptr(prev_guide), ptr(tgt), ptr(prev_tgt), ptr(vec), B, h, w, block, tl, ptr(scratch), ptr(out),
                               current_stream()), "flicker_u8")
     return out
@@ -821,19 +790,12 @@ def image_ciede2000(a, b, map=None, out=None):
     True (a fresh (B,H,W) float32 tensor) or the caller's contiguous (B,H,W) float32 CUDA tensor for the per-pixel values; with a map the result is
     (means, map).  out: the caller's contiguous (B,) float64 CUDA tensor.  The means are the same bits with and without a map, at every batch size
     and on every stream."""
-    _cuda(a, b)
     if a.dim() == 3:
         a, b = a[None], b[None]
-    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
-        raise ValueError("image_ciede2000: the two images differ in shape, dtype or device: %s %s against %s %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
-    if a.dim() != 4 or a.shape[3] != 3 or a.dtype != torch.uint8 or min(a.shape) < 1:
-        raise ValueError("image_ciede2000 needs (B,H,W,3) uint8 images, got %s %s" % (tuple(a.shape), a.dtype))
+    _rgb_pair("image_ciede2000", a=a, b=b)
     B, H, W, _ = a.shape
     lib = _lib.load()
-    nbytes = lib.cfen_ciede2000_bytes(B, H, W)
-    if nbytes == 0:
-        raise ValueError("image_ciede2000: %d images of %d x %d are outside the limits (B <= 65535, H, W <= 65536)" % (B, H, W))
-    scratch = _f64_scratch(nbytes, a.device)
+    scratch = _scratch_for("image_ciede2000", lib.cfen_ciede2000_bytes, (B, H, W), a.device, "B <= 65535, H, W <= 65536")
     if map is True:
         map = torch.empty(B, H, W, dtype=torch.float32, device=a.device)
     elif map is not None:
@@ -848,27 +810,13 @@ NOREF_RECORD_BYTES = 2080                 # CFEN_NOREF_RECORD_BYTES
 NOREF_MAX_RADIUS = 16                     # CFEN_NOREF_MAX_RADIUS
 
 
-def _noref_images(what, *images):
-    _cuda(*images)
-    first = images[0]
-    for t in images:
-        if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8 or min(t.shape) < 1:
-            raise ValueError("%s needs (B,H,W,3) uint8 images, got %s %s" % (what, tuple(t.shape), t.dtype))
-        if t.shape != first.shape or t.device != first.device:
-            raise ValueError("%s: the two images differ in shape or device: %s against %s" % (what, tuple(first.shape), tuple(t.shape)))
-
-
 def _noref(what, hazy, out, radius, map_hazy, map_out):
     """cfen_noref_u8 on the pairs (hazy, out): (counts, grad, dark_hazy, dark_out), a map that was not asked for None"""
-    _noref_images(what, hazy, out)
+    _rgb_pair(what, hazy=hazy, out=out)
     B, H, W, _ = hazy.shape
     dev = hazy.device
     lib = _lib.load()
-    nbytes = lib.cfen_noref_bytes(B, H, W, int(radius))
-    if nbytes == 0:
-        raise ValueError("%s: %d images of %d x %d at radius %s are outside the limits (B <= 65535, H, W <= 65536, radius 0 .. %d)"
-                         % (what, B, H, W, radius, NOREF_MAX_RADIUS))
-    scratch = _f64_scratch(nbytes, dev)
+    scratch = _scratch_for(what, lib.cfen_noref_bytes, (B, H, W, int(radius)), dev, "B <= 65535, H, W <= 65536, radius 0 .. %d" % NOREF_MAX_RADIUS)
     counts = torch.empty(B, 2, 259, dtype=torch.int64, device=dev)
     grad = torch.empty(B, 2, dtype=torch.float64, device=dev)
     d0 = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if map_hazy else None
@@ -965,9 +913,7 @@ def rgb_to_yuv_u8(rgb, chroma, matrix="bt601", full_range=False, out=None):
     single = rgb.dim() == 3
     if single:
         rgb = rgb[None]
-    _cuda(rgb)
-    if rgb.dim() != 4 or rgb.shape[3] != 3 or rgb.dtype != torch.uint8 or min(rgb.shape) < 1:
-        raise ValueError("rgb_to_yuv_u8 needs (B,H,W,3) uint8 images, got %s %s" % (tuple(rgb.shape), rgb.dtype))
+    _rgb_batch("rgb_to_yuv_u8", rgb=rgb)
     B, H, W, _ = rgb.shape
     lib = _lib.load()
     nbytes = lib.cfen_yuv_frame_bytes(H, W, code)

@@ -30,6 +30,23 @@ def test_header_symbols_are_exported_and_bound():
     assert _lib.load().cfen_abi_version() == 1
 
 
+def test_every_header_has_its_own_table_and_the_tables_are_apart():
+    """the ledger of _lib.HEADERS: every header under include/ that declares a function has a table, every table holds exactly what its header
+    declares, no two tables share a name, and the core is the frozen one.  A new header fails here until it has a table of its own."""
+    import glob
+    import itertools
+    import cabi_ledger
+    _lib = cabi_ledger.library()
+    declared = {os.path.basename(p): cabi_ledger.header_functions(os.path.basename(p)) for p in glob.glob(os.path.join(ROOT, "include", "cfen_*.h"))}
+    assert {h for h, fns in declared.items() if fns} == set(_lib.HEADERS)
+    for (h1, t1), (h2, t2) in itertools.combinations(_lib.HEADERS.items(), 2):
+        assert not set(t1) & set(t2), (h1, h2)
+    for header, table in _lib.HEADERS.items():
+        assert sorted(declared[header]) == sorted(table), header
+    assert _lib.SIGNATURES is _lib.HEADERS["cfen_hip.h"] and len(_lib.SIGNATURES) == 68 and sorted(_lib.SIGNATURES) == declared_symbols()
+    assert _lib.load().cfen_abi_version() == 1
+
+
 def test_argument_errors_do_not_need_a_gpu():
     from cfen_vit_dehazing_amd import _lib
     lib = _lib.load()

@@ -2,15 +2,13 @@
 and Dalal and against anchors of the byte-to-dE chain, the sRGB table the kernel is handed, the header's ledger, the argument errors of the
 entry point, the --eval_ciede2000 option and the csv / summary text with the extra column.  No GPU."""
 import ctypes
-import os
-import re
+import functools
 
 import numpy as np
 import pytest
 
+import cabi_ledger
 import ciede_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- the restatement ---------------------------------------------------------------------------------------------------------------------------------
@@ -73,40 +71,8 @@ def test_srgb_linear_table():
 
 
 # ---- the header's ledger ---------------------------------------------------------------------------------------------------------------------------
-def colordiff_header_functions():
-    """{function: number of parameters} of include/cfen_colordiff.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_colordiff.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
 def test_colordiff_header_is_exported_bound_and_apart_from_the_frozen_abi():
-    from cfen_vit_dehazing_amd import _lib
-    from cfen_vit_dehazing_amd import build
-    import test_cabi
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    fns = colordiff_header_functions()
-    assert fns == {"cfen_ciede2000_bytes": 3, "cfen_ciede2000_u8": 10}
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    assert sorted(_lib.COLORDIFF_SIGNATURES) == sorted(fns)
-    for name, nargs in fns.items():
-        assert hasattr(raw, name), "libcfen_hip.so does not export %s" % name
-        res, args = _lib.COLORDIFF_SIGNATURES[name]
-        assert len(args) == nargs, name
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    old = test_cabi.declared_symbols()
-    for other in (old, _lib.SIGNATURES, _lib.EXTENSION_SIGNATURES, _lib.GUIDED_SIGNATURES):
-        assert not set(fns) & set(other)
-    assert "ciede" not in open(os.path.join(ROOT, "include", "cfen_hip.h")).read()
-    assert len(_lib.SIGNATURES) == len(old) == 68
-    assert sorted(_lib.EXTENSION_SIGNATURES) == ["cfen_resample_u8"] and sorted(_lib.GUIDED_SIGNATURES) == ["cfen_guided_apply_u8", "cfen_guided_coef_u8"]
-    assert lib.cfen_abi_version() == 1
-    assert "k_colordiff.hip" in build.SOURCES
+    cabi_ledger.check_header_bound("cfen_colordiff.h", {"cfen_ciede2000_bytes": 3, "cfen_ciede2000_u8": 10}, word="ciede")
 
 
 def test_scratch_size_is_one_double_per_1024_pixels():
@@ -122,11 +88,7 @@ def test_argument_errors_do_not_need_a_gpu():
     from cfen_vit_dehazing_amd import _lib
     lib = _lib.load()
     a, b, tab, scr, mp, out, z = (ctypes.c_void_p(v) for v in (1 << 20, 2 << 20, 3 << 20, 4 << 20, 5 << 20, 6 << 20, 0))      # never dereferenced
-
-    def refused(what, *args):
-        assert lib.cfen_ciede2000_u8(*args) == -1
-        err = lib.cfen_last_error()
-        assert b"ciede2000_u8" in err and what in err, err
+    refused = functools.partial(cabi_ledger.refused, lib, "ciede2000_u8")
 
     for bad in ((z, b, tab, scr, out), (a, z, tab, scr, out), (a, b, z, scr, out), (a, b, tab, z, out), (a, b, tab, scr, z)):
         refused(b"null pointer", bad[0], bad[1], 1, 4, 4, bad[2], bad[3], mp, bad[4], z)

@@ -3,6 +3,7 @@ measure on the synthetic clips of DESIGN sections 18 and 20 (where the true came
 --eval_flicker options of dehaze_video.py, the csv and summary formats, the header's ledger and the argument errors of the two entry points.
 No GPU."""
 import ctypes
+import functools
 import math
 import os
 import re
@@ -10,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+import cabi_ledger
 import flicker_ref as ref
 import motion_ref
 import temporal_ref
@@ -234,42 +236,10 @@ def test_csv_and_summary_formats():
 
 
 # ---- the new header's ledger -------------------------------------------------------------------------------------------------------------------------
-def flicker_header_functions():
-    """{function: number of parameters} of include/cfen_flicker.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_flicker.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
 def test_flicker_header_is_exported_bound_and_apart_from_the_older_tables():
-    from cfen_vit_dehazing_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    fns = flicker_header_functions()
-    assert fns == {"cfen_flicker_bytes": 3, "cfen_flicker_u8": 13}
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    assert sorted(_lib.FLICKER_SIGNATURES) == sorted(fns)
-    for name, nargs in fns.items():
-        assert hasattr(raw, name), "libcfen_hip.so does not export %s" % name
-        res, args = _lib.FLICKER_SIGNATURES[name]
-        assert len(args) == nargs, name
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    older = (_lib.SIGNATURES, _lib.EXTENSION_SIGNATURES, _lib.GUIDED_SIGNATURES, _lib.COLORDIFF_SIGNATURES, _lib.NOREF_SIGNATURES, _lib.YUV_SIGNATURES,
-             _lib.TEMPORAL_SIGNATURES, _lib.MOTION_SIGNATURES)
-    for table in older:
-        assert not set(fns) & set(table)
-    assert len(_lib.SIGNATURES) == 68 and lib.cfen_abi_version() == 1
-    assert sorted(_lib.MOTION_SIGNATURES) == ["cfen_motion_search_u8", "cfen_motion_warp"]
-    assert "flicker" not in open(os.path.join(ROOT, "include", "cfen_hip.h")).read()
-    assert "k_flicker.hip" in build.SOURCES
-    source = open(os.path.join(ROOT, "tests", "test_hip_flicker.py")).read()          # the guard-band test's text (the module itself needs a GPU)
-    body = re.search(r"\ndef test_guard_bands_flicker\(.*?(?=\n(?:def |@pytest|# ----))", source, flags=re.S)
-    assert body, "tests/test_hip_flicker.py has no test_guard_bands_flicker"
-    assert "lib.cfen_flicker_u8(" in body.group(0) and "lib.cfen_flicker_bytes(" in body.group(0)
+    fns = {"cfen_flicker_bytes": 3, "cfen_flicker_u8": 13}
+    cabi_ledger.check_header_bound("cfen_flicker.h", fns)
+    cabi_ledger.check_guard_band_test_calls("test_hip_flicker.py", "test_guard_bands_flicker", fns)
 
 
 def test_the_definition_stands_in_the_header():
@@ -289,17 +259,7 @@ def test_flicker_argument_errors_do_not_need_a_gpu():
     from cfen_vit_dehazing_amd import _lib
     lib = _lib.load()
     g, pg, t, pt, v, sc, su, z = (ctypes.c_void_p(k << 24) for k in (1, 2, 3, 4, 5, 6, 7, 0))      # never dereferenced
-
-    def call(*a):
-        return lib.cfen_flicker_u8(*a)
-
-    def refused(what, *args):
-        assert call(*args) == -1
-        err = lib.cfen_last_error()
-        assert b"flicker_u8" in err and what in err, err
-
-    def off(q, k):
-        return ctypes.c_void_p(q.value + k)
+    refused, off = functools.partial(cabi_ledger.refused, lib, "flicker_u8"), cabi_ledger.off
 
     for i in (0, 1, 2, 3, 10, 11):
         args = [g, pg, t, pt, v, 1, 20, 20, 8, 8, sc, su, z]

@@ -2,18 +2,16 @@
 torch's bilinear interpolation, the properties of the definition, the synthetic scattering-model experiment of DESIGN section 14, the tolerance
 TAU of tests/test_hip_guided.py, the argument errors of the two entry points, the --fit_refine options, and the header's ledger.  No GPU."""
 import ctypes
+import functools
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_ledger
 import guided_ref as ref
 import resample_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # The tolerance of tests/test_hip_guided.py, in levels (1 = one step of a byte): 8 x the largest |v_float32 - v_float64| of the pre-rounding value v
 # over every case of that file, where float32 is the header's formulas rounded to fp32 step by step on the CPU (guided_ref, dtype=float32) --
@@ -125,11 +123,7 @@ def test_guided_argument_errors_do_not_need_a_gpu():
     lib = _lib.load()
     g, s, tmp, coef, hi, dst, z = (ctypes.c_void_p(v) for v in (1 << 20, 2 << 20, 3 << 20, 4 << 20, 5 << 20, 6 << 20, 0))      # never dereferenced
     f = ctypes.c_float
-
-    def refused(fn, what, *args):
-        assert getattr(lib, "cfen_" + fn)(*args) == -1
-        err = lib.cfen_last_error()
-        assert fn.encode() in err and what in err, err
+    refused = functools.partial(cabi_ledger.refused, lib)
 
     ok = 6.5
     for bad in ((z, s, tmp, coef), (g, z, tmp, coef), (g, s, z, coef), (g, s, tmp, z)):
@@ -206,35 +200,5 @@ def test_refine_arguments_of_the_library_path():
 
 
 # ---- the new header's ledger ------------------------------------------------------------------------------------------------------------------------
-def guided_header_functions():
-    """{function: number of parameters} of include/cfen_guided.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_guided.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
 def test_guided_header_is_exported_bound_and_apart_from_the_frozen_abi():
-    from cfen_vit_dehazing_amd import _lib
-    import test_cabi
-    from test_resample_host import resample_header_functions
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    fns = guided_header_functions()
-    assert fns == {"cfen_guided_coef_u8": 10, "cfen_guided_apply_u8": 9}
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    assert sorted(_lib.GUIDED_SIGNATURES) == sorted(fns)
-    for name, nargs in fns.items():
-        assert hasattr(raw, name), "libcfen_hip.so does not export %s" % name
-        res, args = _lib.GUIDED_SIGNATURES[name]
-        assert len(args) == nargs, name
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    old = test_cabi.declared_symbols()
-    assert not set(fns) & set(old) and not set(fns) & set(_lib.SIGNATURES) and not set(fns) & set(_lib.EXTENSION_SIGNATURES)
-    assert not set(fns) & set(resample_header_functions())
-    assert "guided" not in open(os.path.join(ROOT, "include", "cfen_hip.h")).read()
-    assert len(_lib.SIGNATURES) == len(old) == 68 and sorted(_lib.EXTENSION_SIGNATURES) == ["cfen_resample_u8"]
-    assert lib.cfen_abi_version() == 1
+    cabi_ledger.check_header_bound("cfen_guided.h", {"cfen_guided_coef_u8": 10, "cfen_guided_apply_u8": 9})

@@ -11,7 +11,6 @@ Tolerances (fixed before the kernel ran; a float32 numpy restatement of the head
              (ciede_ref.branch_values), and no image may have more than 1e-3 of its pixels excluded."""
 import ctypes
 import functools
-import inspect
 import os
 
 import numpy as np
@@ -20,10 +19,10 @@ import torch
 
 from cfen_vit_dehazing_amd import _lib, metrics, ops
 from cfen_vit_dehazing_amd.manifest import generate_state_dict
+import cabi_ledger
 import ciede_ref as ref
 import guarded
 import test_hip_metrics as evalref                     # TINY, _run_cli, _dataset: the fixtures of the --eval CLI tests
-from test_ciede_host import colordiff_header_functions
 
 pytestmark = pytest.mark.gpu
 
@@ -198,11 +197,9 @@ def test_guard_bands_ciede():
 
 
 def test_every_function_of_the_colordiff_header_is_guard_band_tested():
-    fns = colordiff_header_functions()
-    assert fns and sorted(fns) == sorted(_lib.COLORDIFF_SIGNATURES)
-    body = inspect.getsource(test_guard_bands_ciede)
-    for sym in fns:
-        assert "lib.%s(" % sym in body, "test_guard_bands_ciede does not call %s" % sym
+    fns = cabi_ledger.header_functions("cfen_colordiff.h")
+    assert sorted(fns) == sorted(_lib.HEADERS["cfen_colordiff.h"])
+    cabi_ledger.check_guard_band_test_calls("test_hip_ciede.py", "test_guard_bands_ciede", fns)
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,6 @@
 fit-to-size inference with refine="guided" on top of it (dec_ipt.forward_fit, test.py --fit --fit_refine guided), and the second half of the
 ledger of include/cfen_guided.h.  The reference is the float64 restatement tests/guided_ref.py; the tolerance TAU (levels) is measured on the CPU in
 tests/test_guided_host.py, never against the kernels; the composition tests have no tolerance."""
-import inspect
 import os
 
 import numpy as np
@@ -12,10 +11,11 @@ from PIL import Image
 
 from cfen_vit_dehazing_amd import _lib, ops
 from cfen_vit_dehazing_amd.manifest import generate_state_dict
+import cabi_ledger
 import guarded
 import guided_ref as ref
 import test_hip_resample as fitref                      # TINY (T = 128), make_net, net_input, plain_u8, _run_cli
-from test_guided_host import TAU, guided_header_functions
+from test_guided_host import TAU
 
 pytestmark = pytest.mark.gpu
 
@@ -206,11 +206,9 @@ def test_guard_bands_guided():
 def test_every_function_of_the_guided_header_is_guard_band_tested():
     """what tests/test_cabi.py checks for include/cfen_hip.h, for include/cfen_guided.h: every function it declares is called through lib. inside
     the guard-band test above"""
-    fns = guided_header_functions()
-    assert fns and sorted(fns) == sorted(_lib.GUIDED_SIGNATURES)
-    body = inspect.getsource(test_guard_bands_guided)
-    for sym in fns:
-        assert "lib.%s(" % sym in body, "test_guard_bands_guided does not call %s" % sym
+    fns = cabi_ledger.header_functions("cfen_guided.h")
+    assert sorted(fns) == sorted(_lib.HEADERS["cfen_guided.h"])
+    cabi_ledger.check_guard_band_test_calls("test_hip_guided.py", "test_guard_bands_guided", fns)
 
 
 # ---- forward_fit(refine="guided") ---------------------------------------------------------------------------------------------------------------------

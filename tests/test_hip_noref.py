@@ -8,7 +8,6 @@ Bars:
                                    N 2^-52 = 2.3e-10 relative.  One dropped position of the 97 x 131 case moves the sum by about 8e-5 relative.
   csv values                       |csv - ref| <= 1e-6: the %.6f rounding (0.5e-6) plus 1e-9 of a gradient of at most 255."""
 import ctypes
-import inspect
 import os
 import shutil
 
@@ -19,10 +18,10 @@ import torch
 from cfen_vit_dehazing_amd import _lib, metrics, ops
 from cfen_vit_dehazing_amd.manifest import generate_state_dict
 from cfen_vit_dehazing_amd.ops import NOREF_TILE_W, NOREF_TILE_H, NOREF_RECORD_BYTES
+import cabi_ledger
 import guarded
 import noref_ref as ref
 import test_hip_metrics as evalref                     # TINY, _run_cli, _dataset: the fixtures of the --eval CLI tests
-from test_noref_host import noref_header_functions
 
 pytestmark = pytest.mark.gpu
 
@@ -154,11 +153,9 @@ def test_guard_bands_noref():
 
 
 def test_every_function_of_the_noref_header_is_guard_band_tested():
-    fns = noref_header_functions()
-    assert fns and sorted(fns) == sorted(_lib.NOREF_SIGNATURES)
-    body = inspect.getsource(test_guard_bands_noref)
-    for sym in fns:
-        assert "lib.%s(" % sym in body, "test_guard_bands_noref does not call %s" % sym
+    fns = cabi_ledger.header_functions("cfen_noref.h")
+    assert sorted(fns) == sorted(_lib.HEADERS["cfen_noref.h"])
+    cabi_ledger.check_guard_band_test_calls("test_hip_noref.py", "test_guard_bands_noref", fns)
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------------------------

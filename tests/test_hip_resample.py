@@ -1,7 +1,6 @@
 """PIL-exact uint8 resampling on the device (cfen_resample_u8, ops.resample_u8), fit-to-size inference on top of it (dec_ipt.forward_fit,
 test.py --fit), and the ledger of include/cfen_resample.h.  The reference of every comparison is Image.resize of the PIL installed here, called
 in the test; there is no tolerance anywhere."""
-import inspect
 import os
 import subprocess
 import sys
@@ -16,9 +15,9 @@ from cfen_vit_dehazing_amd.config import NetConfig
 from cfen_vit_dehazing_amd.data import to_normalized_tensor
 from cfen_vit_dehazing_amd.hipnet import dec_ipt
 from cfen_vit_dehazing_amd.manifest import generate_state_dict
+import cabi_ledger
 import guarded
 import resample_ref as ref
-from test_resample_host import resample_header_functions
 
 pytestmark = pytest.mark.gpu
 
@@ -175,13 +174,11 @@ def test_guard_bands_resample_u8():
 
 
 def test_every_function_of_the_resample_header_is_guard_band_tested():
-    """what tests/test_cabi.py checks for include/cfen_hip.h, for include/cfen_resample.h: every function it declares is called, through ops. or
-    lib., inside the guard-band test above"""
-    fns = resample_header_functions()
-    assert fns and sorted(fns) == sorted(_lib.EXTENSION_SIGNATURES)
-    body = inspect.getsource(test_guard_bands_resample_u8)
-    for sym in fns:
-        assert any(c in body for c in ("ops.%s(" % sym[len("cfen_"):], "lib.%s(" % sym)), "test_guard_bands_resample_u8 does not call %s" % sym
+    """what tests/test_cabi.py checks for include/cfen_hip.h, for include/cfen_resample.h: every function it declares is called through lib.
+    inside the guard-band test above"""
+    fns = cabi_ledger.header_functions("cfen_resample.h")
+    assert sorted(fns) == sorted(_lib.HEADERS["cfen_resample.h"])
+    cabi_ledger.check_guard_band_test_calls("test_hip_resample.py", "test_guard_bands_resample_u8", fns)
 
 
 # ---- forward_fit -------------------------------------------------------------------------------------------------------------------------

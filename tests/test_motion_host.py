@@ -3,12 +3,14 @@ the search (translations found, ties, the bias) and of the compensated recursion
 behind the defaults, the --temporal_mc options of dehaze_video.py, check_mc_params, the header's ledger and the argument
 errors of the two entry points.  No GPU."""
 import ctypes
+import functools
 import os
 import re
 
 import numpy as np
 import pytest
 
+import cabi_ledger
 import motion_ref as ref
 import temporal_ref
 
@@ -247,43 +249,10 @@ def test_check_mc_params():
 
 
 # ---- the new header's ledger ------------------------------------------------------------------------------------------------------------------------
-def motion_header_functions():
-    """{function: number of parameters} of include/cfen_motion.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_motion.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
 def test_motion_header_is_exported_bound_and_apart_from_the_older_tables():
-    from cfen_vit_dehazing_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    fns = motion_header_functions()
-    assert fns == {"cfen_motion_search_u8": 11, "cfen_motion_warp": 9}
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    assert sorted(_lib.MOTION_SIGNATURES) == sorted(fns)
-    for name, nargs in fns.items():
-        assert hasattr(raw, name), "libcfen_hip.so does not export %s" % name
-        res, args = _lib.MOTION_SIGNATURES[name]
-        assert len(args) == nargs, name
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    older = (_lib.SIGNATURES, _lib.EXTENSION_SIGNATURES, _lib.GUIDED_SIGNATURES, _lib.COLORDIFF_SIGNATURES, _lib.NOREF_SIGNATURES, _lib.YUV_SIGNATURES,
-             _lib.TEMPORAL_SIGNATURES)
-    for table in older:
-        assert not set(fns) & set(table)
-    assert len(_lib.SIGNATURES) == 68 and lib.cfen_abi_version() == 1
-    assert sorted(_lib.TEMPORAL_SIGNATURES) == ["cfen_temporal_apply_u8", "cfen_temporal_blend"]
-    assert "motion_search" not in open(os.path.join(ROOT, "include", "cfen_hip.h")).read()
-    assert "k_motion.hip" in build.SOURCES
-    source = open(os.path.join(ROOT, "tests", "test_hip_motion.py")).read()           # the guard-band test's text (the module itself needs a GPU)
-    body = re.search(r"\ndef test_guard_bands_motion\(.*?(?=\n(?:def |@pytest|# ----))", source, flags=re.S)
-    assert body, "tests/test_hip_motion.py has no test_guard_bands_motion"
-    for sym in fns:
-        assert "lib.%s(" % sym in body.group(0), "test_guard_bands_motion does not call %s" % sym
+    fns = {"cfen_motion_search_u8": 11, "cfen_motion_warp": 9}
+    cabi_ledger.check_header_bound("cfen_motion.h", fns, word="motion_search")
+    cabi_ledger.check_guard_band_test_calls("test_hip_motion.py", "test_guard_bands_motion", fns)
 
 
 def test_the_definition_stands_in_the_header():
@@ -300,14 +269,7 @@ def test_motion_argument_errors_do_not_need_a_gpu():
     from cfen_vit_dehazing_amd import _lib
     lib = _lib.load()
     g, p, v, s, st, po, so, z = (ctypes.c_void_p(k << 20) for k in (1, 2, 3, 4, 5, 6, 7, 0))      # never dereferenced
-
-    def refused(fn, what, *args):
-        assert getattr(lib, "cfen_" + fn)(*args) == -1
-        err = lib.cfen_last_error()
-        assert fn.encode() in err and what in err, err
-
-    def off(q, k):
-        return ctypes.c_void_p(q.value + k)
+    refused, off = functools.partial(cabi_ledger.refused, lib), cabi_ledger.off
 
     for bad in ((z, p, v, s), (g, z, v, s), (g, p, z, s), (g, p, v, z)):
         refused("motion_search_u8", b"null pointer", bad[0], bad[1], 1, 20, 20, 8, 2, 4, bad[2], bad[3], z)

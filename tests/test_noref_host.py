@@ -2,6 +2,7 @@
 known answers, the scores of metrics.noref_from_stats, the header's ledger, the scratch size and the argument errors of the entry point, the
 --eval_noref options, the csv / summary text and the float -> byte recovery of the hazy image.  No GPU."""
 import ctypes
+import functools
 import math
 import os
 import re
@@ -9,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import cabi_ledger
 import noref_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -124,45 +126,8 @@ def test_dot_footprint():
 
 
 # ---- the header's ledger ---------------------------------------------------------------------------------------------------------------------------
-def noref_header_functions():
-    """{function: number of parameters} of include/cfen_noref.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_noref.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
-def _lib_built():
-    from cfen_vit_dehazing_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib
-
-
 def test_noref_header_is_exported_bound_and_apart_from_the_frozen_abi():
-    from cfen_vit_dehazing_amd import build
-    import test_cabi
-    _lib = _lib_built()
-    fns = noref_header_functions()
-    assert fns == {"cfen_noref_bytes": 4, "cfen_noref_u8": 12}
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    assert sorted(_lib.NOREF_SIGNATURES) == sorted(fns)
-    for name, nargs in fns.items():
-        assert hasattr(raw, name), "libcfen_hip.so does not export %s" % name
-        res, args = _lib.NOREF_SIGNATURES[name]
-        assert len(args) == nargs, name
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    old = test_cabi.declared_symbols()
-    for other in (old, _lib.SIGNATURES, _lib.EXTENSION_SIGNATURES, _lib.GUIDED_SIGNATURES, _lib.COLORDIFF_SIGNATURES):
-        assert not set(fns) & set(other)
-    assert "noref" not in open(os.path.join(ROOT, "include", "cfen_hip.h")).read()
-    assert len(_lib.SIGNATURES) == len(old) == 68
-    assert (len(_lib.EXTENSION_SIGNATURES), len(_lib.GUIDED_SIGNATURES), len(_lib.COLORDIFF_SIGNATURES)) == (1, 2, 2)
-    assert lib.cfen_abi_version() == 1
-    assert "k_noref.hip" in build.SOURCES
+    cabi_ledger.check_header_bound("cfen_noref.h", {"cfen_noref_bytes": 4, "cfen_noref_u8": 12})
 
 
 def test_tile_shape_and_record_size_are_the_headers():
@@ -177,7 +142,7 @@ def test_tile_shape_and_record_size_are_the_headers():
 
 
 def test_scratch_size_is_one_record_per_tile():
-    q = _lib_built().load().cfen_noref_bytes
+    q = cabi_ledger.library().load().cfen_noref_bytes
     from cfen_vit_dehazing_amd import ops
     tw, th, rec = ops.NOREF_TILE_W, ops.NOREF_TILE_H, ops.NOREF_RECORD_BYTES
     for B, H, W in ((1, 1, 1), (2, 3, 5), (3, 17, 67), (1, th, tw), (1, th + 1, tw), (1, th, tw + 1), (2, 97, 131), (8, 512, 512), (1, 2160, 3840),
@@ -190,13 +155,9 @@ def test_scratch_size_is_one_record_per_tile():
 
 
 def test_argument_errors_do_not_need_a_gpu():
-    lib = _lib_built().load()
+    lib = cabi_ledger.library().load()
     hz, out, scr, cnt, grd, d0, d1, z = (ctypes.c_void_p(v) for v in (1 << 20, 2 << 20, 3 << 20, 4 << 20, 5 << 20, (6 << 20) + 1, (7 << 20) + 3, 0))
-
-    def refused(what, *args):
-        assert lib.cfen_noref_u8(*args) == -1
-        err = lib.cfen_last_error()
-        assert b"noref_u8" in err and what in err, err
+    refused = functools.partial(cabi_ledger.refused, lib, "noref_u8")
 
     for bad in ((z, out, scr, cnt, grd), (hz, z, scr, cnt, grd), (hz, out, z, cnt, grd), (hz, out, scr, z, grd), (hz, out, scr, cnt, z)):
         refused(b"null pointer", bad[0], bad[1], 1, 4, 4, 7, bad[2], bad[3], bad[4], d0, d1, z)

@@ -2,17 +2,16 @@
 installed here, byte for byte; the table invariants the device pass relies on; the --fit refusals; the ledger of include/cfen_resample.h.
 No GPU."""
 import ctypes
-import os
-import re
+import functools
 
 import numpy as np
 import pytest
 from PIL import Image
 
 from cfen_vit_dehazing_amd import resample
+import cabi_ledger
 import resample_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [(1, 1), (2, 3), (7, 5), (16, 16), (31, 47), (64, 64), (100, 37), (129, 255), (460, 620)]
 # cost cap of the sweep: a pair runs when source + target pixels stay under it, which leaves out only the three pairs among the two largest sizes
 # for the three optional filters; the two required filters run every pair
@@ -117,45 +116,15 @@ def test_fit_hands_over_the_decoded_image(tmp_path):
 
 
 # ---- the new header's ledger ----------------------------------------------------------------------------------------------------------------
-def resample_header_functions():
-    """{function: number of parameters} of include/cfen_resample.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_resample.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
 def test_resample_header_is_exported_bound_and_apart_from_the_frozen_abi():
-    from cfen_vit_dehazing_amd import _lib
-    import test_cabi
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    fns = resample_header_functions()
-    assert "cfen_resample_u8" in fns and fns["cfen_resample_u8"] == 15
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    assert sorted(_lib.EXTENSION_SIGNATURES) == sorted(fns)
-    for name, nargs in fns.items():
-        assert hasattr(raw, name), "libcfen_hip.so does not export %s" % name
-        res, args = _lib.EXTENSION_SIGNATURES[name]
-        assert len(args) == nargs, name
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    old = test_cabi.declared_symbols()
-    assert not set(fns) & set(old) and not set(fns) & set(_lib.SIGNATURES)
-    assert len(_lib.SIGNATURES) == len(old) == 68
-    assert lib.cfen_abi_version() == 1
+    cabi_ledger.check_header_bound("cfen_resample.h", {"cfen_resample_u8": 15})
 
 
 def test_resample_argument_errors_do_not_need_a_gpu():
     from cfen_vit_dehazing_amd import _lib
     lib = _lib.load()
     src, tmp, dst, p, z = (ctypes.c_void_p(v) for v in (4096, 8192, 12288, 16384, 0))        # never dereferenced: every call is refused before a launch
-
-    def refused(what, *args):
-        assert lib.cfen_resample_u8(*args) == -1
-        assert b"resample_u8" in lib.cfen_last_error() and what in lib.cfen_last_error(), lib.cfen_last_error()
+    refused = functools.partial(cabi_ledger.refused, lib, "resample_u8")
 
     refused(b"null image pointer", z, 1, 4, 4, p, p, 5, 8, p, p, 5, 8, tmp, dst, z)
     refused(b"batch", src, 0, 4, 4, p, p, 5, 8, p, p, 5, 8, tmp, dst, z)

@@ -2,6 +2,7 @@
 tests/temporal_ref.py, the tolerance TAU_T of tests/test_hip_temporal.py, the synthetic experiment behind the defaults, the
 argument errors of the two entry points, the --temporal options of dehaze_video.py, and the header's ledger.  No GPU."""
 import ctypes
+import functools
 import math
 import os
 import re
@@ -9,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import cabi_ledger
 import guided_ref
 import temporal_ref as ref
 
@@ -163,14 +165,7 @@ def test_temporal_argument_errors_do_not_need_a_gpu():
     lib = _lib.load()
     g, p, c, s, d, hi, src, dst, z = (ctypes.c_void_p(v << 20) for v in (1, 2, 3, 4, 5, 6, 7, 8, 0))      # never dereferenced
     f = ctypes.c_float
-
-    def refused(fn, what, *args):
-        assert getattr(lib, "cfen_" + fn)(*args) == -1
-        err = lib.cfen_last_error()
-        assert fn.encode() in err and what in err, err
-
-    def off(v, k):
-        return ctypes.c_void_p(v.value + k)
+    refused, off = functools.partial(cabi_ledger.refused, lib), cabi_ledger.off
 
     for bad in ((z, p, c, s, d), (g, z, c, s, d), (g, p, z, s, d), (g, p, c, z, d), (g, p, c, s, z)):
         refused("temporal_blend", b"null pointer", bad[0], bad[1], bad[2], 1, 4, 4, 2, f(8), f(0.8), 1, bad[3], bad[4], z)
@@ -272,41 +267,10 @@ def test_stabiliser_arguments():
 
 
 # ---- the new header's ledger ------------------------------------------------------------------------------------------------------------------------
-def temporal_header_functions():
-    """{function: number of parameters} of include/cfen_temporal.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_temporal.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
 def test_temporal_header_is_exported_bound_and_apart_from_the_older_tables():
-    from cfen_vit_dehazing_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    fns = temporal_header_functions()
-    assert fns == {"cfen_temporal_blend": 13, "cfen_temporal_apply_u8": 10}
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    assert sorted(_lib.TEMPORAL_SIGNATURES) == sorted(fns)
-    for name, nargs in fns.items():
-        assert hasattr(raw, name), "libcfen_hip.so does not export %s" % name
-        res, args = _lib.TEMPORAL_SIGNATURES[name]
-        assert len(args) == nargs, name
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    older = (_lib.SIGNATURES, _lib.EXTENSION_SIGNATURES, _lib.GUIDED_SIGNATURES, _lib.COLORDIFF_SIGNATURES, _lib.NOREF_SIGNATURES, _lib.YUV_SIGNATURES)
-    for table in older:
-        assert not set(fns) & set(table)
-    assert len(_lib.SIGNATURES) == 68 and lib.cfen_abi_version() == 1
-    assert "temporal" not in open(os.path.join(ROOT, "include", "cfen_hip.h")).read()
-    assert "k_temporal.hip" in build.SOURCES
-    source = open(os.path.join(ROOT, "tests", "test_hip_temporal.py")).read()         # the guard-band test's text (the module itself needs a GPU)
-    body = re.search(r"\ndef test_guard_bands_temporal\(.*?(?=\n(?:def |@pytest|# ----))", source, flags=re.S)
-    assert body, "tests/test_hip_temporal.py has no test_guard_bands_temporal"
-    for sym in fns:
-        assert "lib.%s(" % sym in body.group(0), "test_guard_bands_temporal does not call %s" % sym
+    fns = {"cfen_temporal_blend": 13, "cfen_temporal_apply_u8": 10}
+    cabi_ledger.check_header_bound("cfen_temporal.h", fns)
+    cabi_ledger.check_guard_band_test_calls("test_hip_temporal.py", "test_guard_bands_temporal", fns)
 
 
 def test_the_definition_stands_in_the_header():

@@ -17,20 +17,12 @@ import numpy as np
 import pytest
 
 from cfen_vit_dehazing_amd import video, yuv
+import cabi_ledger
 import yuv_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMBOS = [("bt601", False), ("bt601", True), ("bt709", False), ("bt709", True)]
 SIZES = [(1, 1), (3, 5), (8, 8)]
-
-
-def yuv_header_functions():
-    """{function: number of parameters} of include/cfen_yuv.h"""
-    text = open(os.path.join(ROOT, "include", "cfen_yuv.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"])
-            for m in re.finditer(r"\b(cfen_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
 
 
 # ---- tables ----------------------------------------------------------------------------------------------------------------------------
@@ -354,22 +346,11 @@ def test_matrix_and_range_choices():
 # ---- the header's ledger ---------------------------------------------------------------------------------------------------------------
 def test_every_function_of_the_yuv_header_is_bound_and_guard_band_tested():
     from cfen_vit_dehazing_amd import _lib
-    fns = yuv_header_functions()
-    assert fns == {"cfen_yuv_frame_bytes": 3, "cfen_yuv_to_rgb_u8": 9, "cfen_rgb_to_yuv_u8": 9}
-    assert sorted(fns) == sorted(_lib.YUV_SIGNATURES)
-    for name, n in fns.items():
-        assert len(_lib.YUV_SIGNATURES[name][1]) == n, name
-    assert not set(_lib.YUV_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EXTENSION_SIGNATURES) | set(_lib.GUIDED_SIGNATURES) |
-                                           set(_lib.COLORDIFF_SIGNATURES) | set(_lib.NOREF_SIGNATURES))
+    fns = {"cfen_yuv_frame_bytes": 3, "cfen_yuv_to_rgb_u8": 9, "cfen_rgb_to_yuv_u8": 9}
+    cabi_ledger.check_header_bound("cfen_yuv.h", fns)
     import ctypes
     assert ctypes.sizeof(_lib.YuvTableC) == 64
-    source = open(os.path.join(ROOT, "tests", "test_hip_yuv.py")).read()          # the guard-band test's text (the module itself needs a GPU)
-    body = re.search(r"\ndef test_guard_bands_yuv\(.*?(?=\n(?:def |@pytest|# ----))", source, flags=re.S)
-    assert body, "tests/test_hip_yuv.py has no test_guard_bands_yuv"
-    for sym in fns:
-        assert "lib.%s(" % sym in body.group(0), "test_guard_bands_yuv does not call %s" % sym
-    from cfen_vit_dehazing_amd import build
-    assert "k_yuv.hip" in build.SOURCES
+    cabi_ledger.check_guard_band_test_calls("test_hip_yuv.py", "test_guard_bands_yuv", fns)
     assert yuv.CHROMA == {"420jpeg": 0, "420mpeg2": 1, "422": 2, "444": 3, "mono": 4}
     text = open(os.path.join(ROOT, "include", "cfen_yuv.h")).read()
     for name, code in yuv.CHROMA.items():
