@@ -68,6 +68,13 @@ class YuvTableC(ctypes.Structure):
     _fields_ = [("coef", ctypes.c_int32 * 9), ("luma_offset", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
 
 
+class Yuv16TableC(ctypes.Structure):
+    """cfen_yuv16_table of include/cfen_yuv16.h, passed by value: 9 coefficients in units of 2^-20, the luma offset, the RGB full scale, the depth,
+    4 reserved zeros"""
+    _fields_ = [("coef", ctypes.c_int32 * 9), ("luma_offset", ctypes.c_int32), ("peak", ctypes.c_int32), ("depth", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
 _I = c_int
 _P = c_void_p
 # {header under include/: {symbol it declares: (restype, argtypes)}}.  cfen_hip.h is the frozen core (cfen_abi_version() == 1); every other header is an
@@ -170,6 +177,12 @@ HEADERS = {
         "cfen_yuv_frame_bytes": (c_size_t, [_I, _I, _I]),
         "cfen_yuv_to_rgb_u8": (_I, [_P, c_size_t, _I, _I, _I, _I, YuvTableC, _P, _P]),
         "cfen_rgb_to_yuv_u8": (_I, [_P, _I, _I, _I, _I, YuvTableC, _P, c_size_t, _P]),
+    },
+    # YCbCr of 9 to 16 bits per sample <-> float RGB
+    "cfen_yuv16.h": {
+        "cfen_yuv16_frame_bytes": (c_size_t, [_I, _I, _I]),
+        "cfen_yuv16_to_rgb_f32": (_I, [_P, c_size_t, _I, _I, _I, _I, Yuv16TableC, _P, _P]),
+        "cfen_rgb_f32_to_yuv16": (_I, [_P, _I, _I, _I, _I, Yuv16TableC, _P, c_size_t, _P]),
     },
     # temporal stabilisation
     "cfen_temporal.h": {

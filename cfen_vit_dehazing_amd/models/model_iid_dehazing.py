@@ -140,6 +140,20 @@ class DECHLGVIT(BaseModel):
         """the inputs are of the generator's own size: take the plain branch of forward() whatever --fit / --tile asked for other sizes"""
         self._fit = self._tile = False
 
+    def use_float_outputs(self):
+        """keep the generator's outputs float32 planes instead of tensor2im's bytes: a driver that quantises them itself (video.py's deep route,
+        include/cfen_yuv16.h) reads them with output_floats()"""
+        self._u8_out = False
+        if hasattr(self.netG, 'output_u8'):
+            self.netG.output_u8 = False
+
+    def output_floats(self):
+        """fake_A of the last test() as (B,3,H,W) float32 in [-1, 1], after use_float_outputs(); the fp32 side of a failed half guard included"""
+        out = self.fake_A
+        if out.dtype == torch.uint8:
+            raise RuntimeError('output_floats() needs use_float_outputs() before the forward: fake_A holds bytes')
+        return out.float().contiguous()
+
     def _score_noref(self):
         """--eval_noref: the decoded hazy bytes at the output's size against the bytes that go into the fake_A PNG"""
         from .. import metrics

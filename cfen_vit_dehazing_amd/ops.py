@@ -38,7 +38,8 @@ def _tensor_arg(what, name, t, shape, dtype, like=None):
     written B, H, W in the message), on the device of the tensor `like` if one is given"""
     if not isinstance(t, torch.Tensor) or t.dim() != len(shape) or t.dtype != dtype or (like is not None and t.device != like.device) or \
             any(n < 1 if s is None else n != s for n, s in zip(t.shape, shape)):
-        want = ",".join("BHW"[i + 4 - len(shape)] if s is None else str(s) for i, s in enumerate(shape))
+        free = iter("BHW"[3 - sum(s is None for s in shape):])        # the free sizes in order: (B,H,W,3), (H,W,3), (B,3,H,W)
+        want = ",".join(next(free) if s is None else str(s) for s in shape)
         raise ValueError("%s needs %s as a contiguous (%s) %s tensor%s, got %s" % (
             what, name, want, str(dtype)[len("torch."):], "" if like is None else " on %s" % like.device,
             "%s %s on %s" % (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
@@ -927,6 +928,88 @@ def rgb_to_yuv_u8(rgb, chroma, matrix="bt601", full_range=False, out=None):
     if out.shape[0] != B or out.device != rgb.device:
         raise ValueError("rgb_to_yuv_u8: out holds %d frames on %s for %d images on %s" % (out.shape[0], out.device, B, rgb.device))
     check(lib.cfen_rgb_to_yuv_u8(ptr(rgb), B, H, W, code, _yuv_table_for(matrix, bool(full_range), False), ptr(out), stride, current_stream()), "rgb_to_yuv_u8")
+    return out[0] if single else out
+
+
+def yuv16_table(coef, oy, peak, depth):
+    """a cfen_yuv16_table (include/cfen_yuv16.h) from a (3,3) integer table of yuv.tables(shift=20) and yuv.levels(depth): passed by value"""
+    t = _lib.Yuv16TableC()
+    flat = [int(v) for row in coef for v in row]
+    if len(flat) != 9:
+        raise ValueError("yuv16_table needs a 3 x 3 table, got %d entries" % len(flat))
+    for k, v in enumerate(flat):
+        t.coef[k] = v
+    t.luma_offset, t.peak, t.depth = int(oy), int(peak), int(depth)
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def _yuv16_table_for(matrix, full_range, depth, inverse):
+    """the forward or inverse 2^-20 table of yuv.tables as a cfen_yuv16_table, built once per (matrix, range, depth, direction)"""
+    from . import yuv
+    fwd, inv, _ = yuv.tables(matrix, full_range, shift=yuv.DEEP_SHIFT)
+    oy, peak, _ = yuv.levels(depth, full_range)
+    return yuv16_table(inv if inverse else fwd, oy, peak, depth)
+
+
+def _yuv16_depth(what, depth):
+    from . import yuv
+    return _int_arg(what, "depth", depth, yuv.MIN_DEPTH, yuv.MAX_DEPTH)
+
+
+def yuv16_to_rgb_f32(frames, H, W, chroma, depth, matrix="bt601", full_range=False, out=None):
+    """cfen_yuv16_to_rgb_f32 (include/cfen_yuv16.h): B planar YCbCr frames of `depth` (9 .. 16) bits per sample -- the FRAME payloads of a deep
+    .y4m stream as they are, (B, frame_bytes) uint8 holding little-endian 16-bit samples, rows any even number >= frame_bytes of bytes apart, at
+    an even address -- to (B,3,H,W) float32 RGB in [-1, 1], the layout the generator takes.  A 1-D tensor is one frame and gives (3,H,W).  One
+    launch, 64-bit integer arithmetic and one IEEE division per value: the same bits at every batch size, stride, alignment and stream."""
+    from . import yuv
+    code = yuv.chroma_code(chroma)
+    depth = _yuv16_depth("yuv16_to_rgb_f32", depth)
+    single = isinstance(frames, torch.Tensor) and frames.dim() == 1
+    if single:
+        frames = frames[None]
+    lib = _lib.load()
+    nbytes = lib.cfen_yuv16_frame_bytes(int(H), int(W), code)
+    if nbytes == 0:
+        raise ValueError("yuv16_to_rgb_f32: frames of %s x %s are outside the limits (H, W in 1 .. %d)" % (H, W, yuv.MAX_EDGE))
+    stride = _yuv_frames("yuv16_to_rgb_f32", frames, nbytes)
+    B = frames.shape[0]
+    if out is not None and single:
+        out = out[None]
+    out = _out(out, (B, 3, H, W), torch.float32, frames.device, "yuv16_to_rgb_f32")
+    check(lib.cfen_yuv16_to_rgb_f32(ptr(frames), stride, B, int(H), int(W), code, _yuv16_table_for(matrix, bool(full_range), depth, True), ptr(out),
+                                    current_stream()), "yuv16_to_rgb_f32")
+    return out[0] if single else out
+
+
+def rgb_f32_to_yuv16(rgb, chroma, depth, matrix="bt601", full_range=False, out=None):
+    """cfen_rgb_f32_to_yuv16: (B,3,H,W) float32 CUDA images in [-1, 1] (float16 images are converted with .float(); values outside clamp, NaN is
+    black) to B planar YCbCr frames of `depth` bits per sample, (B, frame_bytes) uint8 (a (3,H,W) image gives a 1-D frame).  out: the caller's
+    (B, frame_bytes) tensor, rows at least a frame apart (the bytes between two frames are not written).  The floats are rounded to nearest, half
+    to even; chroma planes are filtered from the converted values."""
+    from . import yuv
+    code = yuv.chroma_code(chroma)
+    depth = _yuv16_depth("rgb_f32_to_yuv16", depth)
+    single = isinstance(rgb, torch.Tensor) and rgb.dim() == 3
+    if single:
+        rgb = rgb[None]
+    if isinstance(rgb, torch.Tensor) and rgb.dtype == torch.float16:
+        rgb = rgb.float()
+    _tensor_arg("rgb_f32_to_yuv16", "rgb", rgb, (None, 3, None, None), torch.float32)
+    B, _, H, W = rgb.shape
+    lib = _lib.load()
+    nbytes = lib.cfen_yuv16_frame_bytes(H, W, code)
+    if nbytes == 0:
+        raise ValueError("rgb_f32_to_yuv16: images of %d x %d are outside the limits (H, W in 1 .. %d)" % (H, W, yuv.MAX_EDGE))
+    if out is None:
+        out = torch.empty(B, nbytes, dtype=torch.uint8, device=rgb.device)
+    elif single and out.dim() == 1:
+        out = out[None]
+    stride = _yuv_frames("rgb_f32_to_yuv16 (out)", out, nbytes)
+    if out.shape[0] != B or out.device != rgb.device:
+        raise ValueError("rgb_f32_to_yuv16: out holds %d frames on %s for %d images on %s" % (out.shape[0], out.device, B, rgb.device))
+    check(lib.cfen_rgb_f32_to_yuv16(ptr(rgb), B, H, W, code, _yuv16_table_for(matrix, bool(full_range), depth, False), ptr(out), stride,
+                                    current_stream()), "rgb_f32_to_yuv16")
     return out[0] if single else out
 
 

@@ -4,6 +4,7 @@
     forwards (hipnet.forward_tiled_many), which test.py reaches through --tile_pack.
   * --u8_input is always on: the converted frames are bytes.
   * --in_flight stays 1: the loop has its own reader and writer threads (--video_buffers).
+  * --video_depth auto lets a stream of 9 to 16 bits per sample in (the float route of video.run); the default, 8, refuses it as always.
   * the options are recorded in <checkpoints_dir>/<name>/video_opt.txt; opt.txt, which test.py writes, is left as it was."""
 import os
 
@@ -20,6 +21,10 @@ class VideoOptions(TestOptions):
                        help='YCbCr matrix of the stream; auto: bt709 for frames of 720 rows or more, bt601 below (a y4m header does not say)')
         p.add_argument('--video_range', default='auto', choices=('auto', 'limited', 'full'),
                        help='sample range of the stream; auto: the XCOLORRANGE tag of the header, limited (16 .. 235) without one')
+        p.add_argument('--video_depth', default='8', choices=('8', 'auto'),
+                       help='(extension) bits per sample the stream may have: 8 refuses every deeper stream, as always; auto reads the depth of the '
+                            "header's C tag (C420p10, C444p12, Cmono16, ...: 9 to 16 bits) and takes such a stream through the float route "
+                            '(DESIGN section 23), which has no --fit, --temporal, --eval_noref or --eval_flicker yet. An 8-bit stream runs as without the flag')
         p.add_argument('--video_buffers', type=int, default=4, help='slots of the ring of pinned host buffers between the reader, the device and the writer (each holds a batch both ways)')
         p.add_argument('--noref_csv', type=str, default=None, help='--eval_noref: where noref.csv goes (default: beside --out; required when --out is -)')
         p.add_argument('--temporal', action='store_true',
@@ -99,6 +104,11 @@ class VideoOptions(TestOptions):
         defaults = {'mc': temporal.MC_DEFAULTS['range'], 'mc_block': temporal.MC_DEFAULTS['block'], 'mc_bias': temporal.MC_DEFAULTS['bias']}
         return [a for k in defaults if k not in given for a in ('--temporal_' + k, str(defaults[k]))]
 
+    @staticmethod
+    def _without_video_depth(text):
+        """a run without --video_depth prints and records what it always did"""
+        return ''.join(l for l in text.splitlines(True) if not l.startswith('video_depth'))
+
     FLICKER = ('range', 'block', 'bias', 'tol', 'down')
 
     @staticmethod
@@ -162,6 +172,14 @@ class VideoOptions(TestOptions):
             raise ValueError('--eval_noref with --out -: say where noref.csv goes with --noref_csv PATH')
         if first.noref_csv and not first.eval_noref:
             raise ValueError('--noref_csv is where --eval_noref writes: it needs --eval_noref')
+        if first.video_depth == 'auto' and first.video_in != '-':
+            # a file: its header is read here, so that a deep stream with a flag of the uint8 machinery is refused at parsing (a pipe: video.run
+            # refuses as soon as it has read the header)
+            from .. import video
+            tag = video.peek_deep_tag(first.video_in)
+            if tag is not None:
+                video.refuse_deep_flags(first, tag)
+        depth_given = first.video_depth != '8'
         extra_temporal = self._check_temporal(first) + self._check_temporal_mc(first) + self._check_flicker(first)
         mc_on = bool(first.temporal and first.temporal_mc)
         # test.py's own checks run on what test.py would be given: frames in order, and --tile there means one image per call.  What that parse
@@ -184,6 +202,7 @@ class VideoOptions(TestOptions):
         text = text if first.temporal else self._without_temporal(text)
         text = text if mc_on else self._without_temporal_mc(text)
         text = text if first.eval_flicker else self._without_flicker(text)
+        text = text if depth_given else self._without_video_depth(text)
         sys.stdout.write(text)
         sys.stdout.flush()
         if opt.dist_rank == 0:
@@ -192,6 +211,7 @@ class VideoOptions(TestOptions):
                 recorded = recorded if first.temporal else self._without_temporal(recorded)
                 recorded = recorded if mc_on else self._without_temporal_mc(recorded)
                 recorded = recorded if first.eval_flicker else self._without_flicker(recorded)
+                recorded = recorded if depth_given else self._without_video_depth(recorded)
                 if before is None:
                     os.remove(opt_txt)
                 else:

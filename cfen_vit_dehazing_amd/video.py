@@ -2,7 +2,8 @@
 
 A y4m stream is one text line (`YUV4MPEG2 W.. H.. F.. I.. A.. C.. X..`) and then, per frame, a `FRAME` line and the planes Y, Cb, Cr as raw
 bytes -- what `ffmpeg -f yuv4mpegpipe`, x264, aomenc and vmaf read and write.  The frame bytes go to the device as they are; the colour
-conversion both ways runs there (ops.yuv_to_rgb_u8 / ops.rgb_to_yuv_u8, include/cfen_yuv.h) next to the forward.
+conversion both ways runs there (ops.yuv_to_rgb_u8 / ops.rgb_to_yuv_u8, include/cfen_yuv.h) next to the forward.  A stream of 9 to 16 bits per
+sample (--video_depth auto) takes the same loop on floats: ops.yuv16_to_rgb_f32 / ops.rgb_f32_to_yuv16 (include/cfen_yuv16.h), no bytes on the way.
 
 Threads: one reader fills pinned host buffers, one writer drains them; the main thread issues, per batch and on ONE stream, the copy in, the
 conversion, the forward, the conversion back and the copy out.  The ring holds --video_buffers slots; a slot goes reader -> main -> writer ->
@@ -17,6 +18,11 @@ from . import yuv
 
 MAX_HEADER = 8192
 ACCEPTED_C = ("420jpeg", "420mpeg2", "422", "444", "mono")
+# The deep C tags mjpegtools / ffmpeg define, read with max_depth = 16: {tag value: (chroma, depth)}.  C420pN is read as 4:2:0 CO-SITED (the taps of
+# 420mpeg2): chroma on the even columns, between the rows -- the siting of H.264 / HEVC / AV1 output, which is where deep footage comes from (the
+# tag itself does not say).  There is no Cmono14.
+DEEP_C = dict([("%sp%d" % (c, d), ({"420": "420mpeg2"}.get(c, c), d)) for d in yuv.DEPTHS for c in ("420", "422", "444")] +
+              [("mono%d" % d, ("mono", d)) for d in yuv.DEPTHS if d != 14])
 
 
 class Y4MError(ValueError):
@@ -32,15 +38,16 @@ def _open(target, mode):
     return open(target, mode), True
 
 
-def parse_header(line):
-    """the fields of a `YUV4MPEG2 ...` line (bytes, with or without its newline) as a dict: width, height, chroma (one of ACCEPTED_C),
-    color_range ('full' | 'limited' | None), tags (every token after the magic).  Y4MError names the tag this project does not read."""
+def parse_header(line, max_depth=8):
+    """the fields of a `YUV4MPEG2 ...` line (bytes, with or without its newline) as a dict: width, height, chroma (one of ACCEPTED_C), depth (8, or
+    that of a DEEP_C tag when max_depth allows it), ctag (the C tag as written, or None), color_range ('full' | 'limited' | None), tags (every token
+    after the magic).  Y4MError names the tag this project does not read."""
     text = line.rstrip(b"\n").decode("ascii", "replace")
     tokens = text.split(" ")
     if tokens[0] != "YUV4MPEG2":
         raise Y4MError("not a YUV4MPEG2 stream: the first line starts with %r" % text[:16])
     tags = [t for t in tokens[1:] if t]
-    info = {"width": None, "height": None, "chroma": "420jpeg", "color_range": None, "tags": tags}
+    info = {"width": None, "height": None, "chroma": "420jpeg", "depth": 8, "ctag": None, "color_range": None, "tags": tags}
     for t in tags:
         key, value = t[0], t[1:]
         if key in "WH":
@@ -51,11 +58,16 @@ def parse_header(line):
             if value not in ("p", "?"):
                 raise Y4MError("y4m header: interlaced stream (tag %r): only progressive frames (Ip) are dehazed" % t)
         elif key == "C":
+            info["ctag"] = t
             if value == "420":
                 value = "420jpeg"                      # mjpegtools: a plain 420 is 420jpeg
+            if value in DEEP_C and DEEP_C[value][1] <= max_depth:
+                info["chroma"], info["depth"] = DEEP_C[value]
+                continue
             if value not in ACCEPTED_C:
                 why = "high bit depth" if "p1" in value or value.endswith("p9") else ("PAL-DV chroma siting" if value == "420paldv" else "unknown chroma format")
-                raise Y4MError("y4m header: tag %r (%s) is not supported: 8-bit %s only" % (t, why, ", ".join("C" + c for c in ACCEPTED_C)))
+                deep = "" if max_depth <= 8 else " and C420pN, C422pN, C444pN, CmonoN for N in %s" % (tuple(d for d in yuv.DEPTHS if d <= max_depth),)
+                raise Y4MError("y4m header: tag %r (%s) is not supported: 8-bit %s only%s" % (t, why, ", ".join("C" + c for c in ACCEPTED_C), deep))
             info["chroma"] = value
         elif t.startswith("XCOLORRANGE="):
             r = t.split("=", 1)[1].upper()
@@ -78,17 +90,19 @@ def _check_frame_line(line, index):
 
 class Y4MReader:
     """frames of a y4m stream, one at a time.  source: a path, '-' (stdin, binary) or a binary file object.  Reads that come back short (a pipe)
-    are continued.  `header` is the first line byte for byte, with its newline."""
+    are continued.  `header` is the first line byte for byte, with its newline.  max_depth: 8 refuses every deep stream, 16 reads the DEEP_C tags;
+    `depth` is then the bits per sample and `frame_bytes` counts two bytes per sample."""
 
-    def __init__(self, source):
+    def __init__(self, source, max_depth=8):
         self._f, self._own = _open(source, "rb")
         line = self._f.readline(MAX_HEADER)
         if not line.endswith(b"\n"):
             raise Y4MError("y4m header: no end of line within %d bytes" % MAX_HEADER if len(line) >= MAX_HEADER else "y4m header: the stream ends inside it")
         self.header = line
-        info = parse_header(line)
+        info = parse_header(line, max_depth)
         self.width, self.height, self.chroma, self.color_range, self.tags = (info[k] for k in ("width", "height", "chroma", "color_range", "tags"))
-        self.frame_bytes = yuv.frame_bytes(self.height, self.width, self.chroma)
+        self.depth, self.ctag = info["depth"], info["ctag"]
+        self.frame_bytes = yuv.frame_bytes(self.height, self.width, self.chroma, self.depth)
         self.frames_read = 0
 
     def _fill(self, view):
@@ -282,6 +296,29 @@ def pump(reader, writer, batch, slots, process, seconds=None):
     return frames
 
 
+DEEP_REFUSED = ("fit", "temporal", "eval_noref", "eval_flicker")      # uint8 machinery: open for deep streams
+
+
+def refuse_deep_flags(opt, ctag):
+    """a stream of more than 8 bits per sample takes the float route, which has no --fit, --temporal, --eval_noref or --eval_flicker yet: Y4MError
+    naming the stream's tag and the flag"""
+    asked = ["--" + f for f in DEEP_REFUSED if getattr(opt, f, False)]
+    if asked:
+        raise Y4MError("the stream is %s (more than 8 bits per sample) and %s %s given: %s work on uint8 frames only and the deep route has none "
+                       "of them yet; run without, or convert the stream to 8 bits" % (ctag, ", ".join(asked), "is" if len(asked) == 1 else "are",
+                                                                                      ", ".join("--" + f for f in DEEP_REFUSED)))
+
+
+def peek_deep_tag(path):
+    """the C tag of the y4m file at `path` if it is one of DEEP_C, else None (also for anything that is not a readable y4m file: run() says why)"""
+    try:
+        with open(path, "rb") as f:
+            info = parse_header(f.readline(MAX_HEADER), max_depth=16)
+    except (OSError, Y4MError):
+        return None
+    return info["ctag"] if info["depth"] > 8 else None
+
+
 class UnsafeHalfFrames(Y4MError):
     """--precision half: a guard check failed after fp16 frames had already left in the stream"""
 
@@ -293,19 +330,25 @@ def run(opt, log=print):
     from . import metrics, ops
     from .models import create_model
 
-    reader = Y4MReader(opt.video_in)
-    H, W, chroma = reader.height, reader.width, reader.chroma
+    deep_allowed = getattr(opt, "video_depth", "8") == "auto"
+    reader = Y4MReader(opt.video_in, max_depth=16 if deep_allowed else 8)
+    H, W, chroma, depth = reader.height, reader.width, reader.chroma, reader.depth
+    deep = depth > 8
+    if deep:
+        refuse_deep_flags(opt, reader.ctag)   # a pipe: as soon as the header is read, before the checkpoint is loaded and before any output
     matrix = pick_matrix(opt.video_matrix, H)
     full = pick_range(opt.video_range, reader.color_range) == "full"
-    log("video: %d x %d C%s, matrix %s (%s), range %s (%s)" % (W, H, chroma, matrix, "auto: H >= 720 is bt709" if opt.video_matrix == "auto" else "given",
-                                                               "full" if full else "limited",
-                                                               ("auto: XCOLORRANGE" if reader.color_range else "auto: no XCOLORRANGE tag") if opt.video_range == "auto" else "given"))
+    log("video: %d x %d C%s%s, matrix %s (%s), range %s (%s)" % (W, H, chroma, ", %d bits per sample (%s)" % (depth, "float route" if deep else "uint8 route")
+                                                                 if deep_allowed else "", matrix,
+                                                                 "auto: H >= 720 is bt709" if opt.video_matrix == "auto" else "given",
+                                                                 "full" if full else "limited",
+                                                                 ("auto: XCOLORRANGE" if reader.color_range else "auto: no XCOLORRANGE tag") if opt.video_range == "auto" else "given"))
     from .config import VARIANTS, FULL_RES_VARIANTS
     T = opt.loadSize if VARIANTS.get(opt.model_G, "v3") in FULL_RES_VARIANTS else 2 * opt.loadSize      # the generator's image edge (as in test.py)
     route = "plain" if (H, W) == (T, T) else ("fit" if opt.fit else ("tile" if opt.tile else None))
     if route is None:
-        raise Y4MError("the frames are %d x %d but the generator takes %d x %d: give --fit (one resampled forward per frame) or --tile "
-                       "(overlapping tiles)" % (W, H, T, T))
+        raise Y4MError("the frames are %d x %d but the generator takes %d x %d: give %s--tile (overlapping tiles)"
+                       % (W, H, T, T, "" if deep else "--fit (one resampled forward per frame) or "))
     n_known = reader.check_whole_file()       # a file cut short is refused here, before any forward
     model = create_model(opt)
     model.setup(opt)
@@ -315,6 +358,8 @@ def run(opt, log=print):
         raise RuntimeError("the generator's image size is %d, expected %d" % (net.cfg.image_size, T))
     if route == "plain":
         model.use_native_size_route()         # frames of the generator's own size: the plain --u8_input route whatever was asked for other sizes
+    if deep:
+        model.use_float_outputs()             # the deep route quantises the generator's floats itself (ops.rgb_f32_to_yuv16)
     nb, B = reader.frame_bytes, opt.batchSize
     dev = model.device
     stream = torch.cuda.current_stream()
@@ -325,7 +370,7 @@ def run(opt, log=print):
         slots.append(Slot(pins[0].numpy(), pins[1].numpy(), extra=pins))
     d_in = torch.empty(B, nb, dtype=torch.uint8, device=dev)
     d_out = torch.empty(B, nb, dtype=torch.uint8, device=dev)
-    rgb = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+    rgb = torch.empty((B, 3, H, W) if deep else (B, H, W, 3), dtype=torch.float32 if deep else torch.uint8, device=dev)
     noref_rows = []
     seconds = {"wait_for_frames": 0.0, "issue": 0.0, "noref": 0.0}
     actnorm = {"ready": False}                # asked of the device until it is true, then remembered (the layers never go back)
@@ -356,6 +401,40 @@ def run(opt, log=print):
         model.set_input({"B": x, "B_paths": ["frame_%06d" % (first + k) for k in range(x.shape[0])]})
         model.test(opt)
         return model.output_bytes()
+
+    def process_deep(s):
+        """the float route of a stream of 9 .. 16 bits per sample: the samples become (n,3,H,W) float32 in [-1, 1] (include/cfen_yuv16.h), the
+        generator's float outputs are rounded to samples of the same depth; nothing on the way is a byte"""
+        n = s.n
+        pin_in, pin_out = s.extra
+        d_in[:n].copy_(pin_in[:n], non_blocking=True)
+        x = ops.yuv16_to_rgb_f32(d_in[:n], H, W, chroma, depth, matrix, full, out=rgb[:n])
+
+        def model_floats(xs, first):
+            model.set_input({"B": xs, "B_paths": ["frame_%06d" % (first + k) for k in range(xs.shape[0])]})
+            model.test(opt)
+            return model.output_floats()
+        if route != "tile":
+            y = model_floats(x, s.first)
+        else:
+            parts, lo = [], 0
+            if not actnorm["ready"]:
+                actnorm["ready"] = model.actnorm_ready()
+            if not actnorm["ready"]:
+                parts.append(model_floats(x[:1], s.first))       # as the uint8 route: the first frame alone initialises the ActNorm layers
+                actnorm["ready"] = model.actnorm_ready()
+                lo = 1
+            if lo < n:
+                with torch.no_grad():
+                    outs = net.forward_tiled_many([x[k] for k in range(lo, n)], overlap=opt.tile_overlap, tile_batch=opt.tile_batch, output_u8=False,
+                                                  self_ensemble=bool(getattr(opt, "self_ensemble", False)))
+                parts.append(torch.stack([o[2].float() for o in outs]))
+            y = parts[0] if len(parts) == 1 else torch.cat(parts)
+        ops.rgb_f32_to_yuv16(y.contiguous(), chroma, depth, matrix, full, out=d_out[:n])
+        pin_out[:n].copy_(d_out[:n], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(stream)
+        return done
 
     def process(s):
         n = s.n
@@ -402,7 +481,7 @@ def run(opt, log=print):
         return done
 
     t_start = time.perf_counter()
-    frames = pump(reader, writer, B, slots, process, seconds)
+    frames = pump(reader, writer, B, slots, process_deep if deep else process, seconds)
     reader.close()
     total = time.perf_counter() - t_start
     if n_known is not None and n_known != frames:
