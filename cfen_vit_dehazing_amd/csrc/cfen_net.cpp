@@ -54,6 +54,37 @@ struct ConvLayer {
   int kind, k, stride, pad, reflect, nsrc, Cin, Cin_real, Cout, Cout_pad, Kpad, nphase, ntaps, out_edge;
   bool tile;   // LDS-tiled kernel, weights "<layer>.wr" in the rows layout
   bool tz;     // Toeplitz 7x7 kernel (tails), weights "<layer>.wz"
+  double flops(int B) const {   // algorithmic, on B images (ConvTranspose 4x4 s2: 2*Cin*Cout*16 per INPUT pixel); an integer below 2^53, so sums of layers are exact in any order
+    const double e = (double)out_edge;
+    return B * (kind == 1 ? 2.0 * Cin_real * Cout * 16.0 * (e / 2) * (e / 2) : 2.0 * Cout * (double)Cin_real * nsrc * k * k * e * e);
+  }
+};
+// How one group of same-shaped transformer blocks runs: decided once per call by cfen_net::route (capabilities found by build() + plan knobs), executed by run_vit_g,
+// which reads no knob.  A new kernel enters the plan as a value of `whole`, `front` or `back`, a condition in route() and launches in the vit_* function of that half.
+struct VitRoute {
+  // PARTS: front half, attention, back half as chosen below.  DUMMY: what-if probe, one launch that holds CUs (outputs invalid).  CHAIN: the GViT GEMMs as two
+  // persistent chains (k_gvit.hip).  WINDOW: the LViT block as one k_lvit_window launch.
+  // GSTREAM: GViT block of embedding dim 384 (level 1) on the LViT-3 stream kernels: 4 x 4 pooled MAP -> k_front3 (patch gather + linear_encoding + residual +
+  // position + LN1 + in_proj, qkv row-major) -> attention -> k_mlp3 (out_proj + LN2 + FFN + mlp_head + fold into the pooled-size map) -> x4
+  // bilinear: 5 launches instead of 10, and the two stream launches are 16 whole-CU workgroups per block -- 2-3x the latency of the GEMM chain and
+  // a fraction of its CU-time, which is what counts with several forwards in flight
+  enum Whole { PARTS, DUMMY, GSTREAM, CHAIN, WINDOW } whole = PARTS;
+  // CHAIN.  "net.gvit_chain" 4: every GEMM its own launch of the chain kernel, never split over K: no grid barrier, no split-K seam;
+  // 5 (round 5 A/B): as 4 with K split so that a launch has ~a workgroup per CU (in-launch split-K seam, no grid barrier)
+  bool per_gemm = false; int team = 1, split_team = 1;   // team: workgroups per block of a persistent launch; split_team: workgroups a phase's K may be split to fill (0: never split)
+  enum Front { FRONT3, EMBED_QKV, FRONT_GEMMS } front = FRONT_GEMMS;   // k_front3 (k_stream.hip) / k_embed_qkv (k_embed.hip) / patchify + embed or gather-in-GEMM, then LN1 + qkv
+  bool gather_in_gemm = false, ln1_fold = false;                      // FRONT_GEMMS
+  bool head_major = false;                                            // the fused front half writes qkv per (window, head) for k_attention_hm
+  enum Back { MLP3, MLP, BACK_GEMMS } back = BACK_GEMMS;               // k_mlp3 (k_stream.hip) / k_mlp (k_mlp.hip) / proj, LN2 + ffn1, ffn2, head1, head2 + fold
+  bool ln2_fold = false, fold_in_gemm = false;                        // BACK_GEMMS
+  bool upsample = false;                                              // GViT: the x4 bilinear launch follows (else the fuse conv reads the low-resolution map)
+};
+// a token GEMM Y = act(X W^T + bias) + R + P for every member of a block group: operand arrays indexed by member, parameters named by suffix (null = absent)
+struct VitGemm {
+  const void* const* X; const char *w, *bias; void* const* R; const char* pos; void* const* Y; int N, K, relu;
+  const CfenTokGather* tg = nullptr;   // the rows of X are gathered from the input map by the loader
+  const char* lnf_s = nullptr;         // Y = act(LN(X) W0^T + b0) with the LayerNorm folded: w / bias name the ".wl" / ".bl" entries, this the ".s" one (packing.ln_folded)
+  bool fold = false;                   // Y's feature (i, j, c) of token m goes to its pixel of the block's target map (v3:1173, 1186)
 };
 
 inline int cs_of(int C) { return cfen_round_up(C, 8); }
@@ -91,7 +122,6 @@ struct cfen_net {
   int gv_launch = 0;               // persistent-chain launches enqueued so far in this forward (each takes its own barrier word)
   static constexpr int GV_SYNC_WORDS = 1024, GV_ERR_WORD = 512;
   std::set<std::string> gvit_low;  // GViT outputs the last forward left at low resolution (x4 bilinear inside the fuse conv, ConvDesc::up4): cfen_net_stage refuses them
-  bool gv_skip_up = false;         // run_vit_g (GViT): leave the block's result in the low-resolution scratch map, no k_upsample4
   bool tail_whole = false;         // ... and the tails' 3x3 outputs too (k_tail_fused)
   bool stages_on_chip = false;     // the last forward kept the us_conv_d01* maps in LDS (k_up_conv3_fused without "net.keep_stages"): cfen_net_stage refuses them
   bool head5 = false;              // head.0.0 can run on k_head5 (reads the network input itself)
@@ -243,7 +273,16 @@ struct cfen_net {
     primed_bytes = ws_bytes;
     return CFEN_OK;
   }
-  int run_vit_g(int ng, const VitCall* c, int scr0);   // group member g uses scratch set scr0 + 2 g
+  // group member g uses scratch set scr0 + 2 g.  skip_up (GViT): leave the block's result in the low-resolution scratch map, no k_upsample4
+  int run_vit_g(int ng, const VitCall* c, int scr0, bool skip_up = false);
+  VitRoute route(const Vit& v, int ng, int M, bool skip_up) const;
+  struct VitCtx;
+  int vit_gemm(VitCtx& c, const char* what, bool priced, double fl, const VitGemm& a);
+  int vit_front(VitCtx& c, const VitRoute& r);
+  int vit_attention(VitCtx& c, bool head_major);
+  int vit_back(VitCtx& c, const VitRoute& r);
+  int vit_window(VitCtx& c);
+  int vit_chain(VitCtx& c, const VitRoute& r);
   int run_level_g(int ng, const char* tags, int l, const std::string* in, const char* extra_res, const std::string* out, hipStream_t sm,
                   hipStream_t sg);
   int run_decoder(float* const* outs, hipStream_t sm, hipStream_t sg);
@@ -358,12 +397,8 @@ int cfen_net::build() {
     need(n + ".proj.w", wbytes(v, v.D, v.Da));
     if (v.ln_fold1) { need(n + ".qkv.wl", wbytes(v, 3 * v.Da, v.D)); need(n + ".qkv.s", (size_t)3 * v.Da * 4); need(n + ".qkv.bl", (size_t)3 * v.Da * 4); }
     if (v.ln_fold2) { need(n + ".ffn1.wl", wbytes(v, v.hidden, v.D)); need(n + ".ffn1.s", (size_t)v.hidden * 4); need(n + ".ffn1.bl", (size_t)v.hidden * 4); }
-    if (v.stream_mlp) {
+    if (v.stream_mlp || v.gstream) {   // the stream kernels' weights: k_mlp3's always, k_front3's at D = 384 (gstream is D = 384; LViT level 2, D = 192, has no stream front)
       if (v.D == 384) { need(n + ".embed.ws", (size_t)v.D * v.D * esz); need(n + ".qkv.ws", (size_t)3 * v.D * v.D * esz); }
-      need(n + ".proj.ws", (size_t)v.D * v.D * esz); need(n + ".ffn.ws", (size_t)2 * v.D * v.hidden * esz); need(n + ".head.ws", (size_t)2 * v.D * v.hidden * esz);
-    }
-    if (v.gstream) {
-      need(n + ".embed.ws", (size_t)v.D * v.D * esz); need(n + ".qkv.ws", (size_t)3 * v.D * v.D * esz);
       need(n + ".proj.ws", (size_t)v.D * v.D * esz); need(n + ".ffn.ws", (size_t)2 * v.D * v.hidden * esz); need(n + ".head.ws", (size_t)2 * v.D * v.hidden * esz);
     }
     if (v.chain) {
@@ -549,9 +584,7 @@ int cfen_net::run_conv_g(int ng, const ConvCall* cc, int act) {
       d[g].res[0] = q.res0.empty() ? nullptr : map_ptr(q.res0);
       d[g].res[1] = q.res1.empty() ? nullptr : map_ptr(q.res1);
     }
-    const double e = (double)c.out_edge;
-    fl += cfg.batch * (c.kind == 1 ? 2.0 * c.Cin_real * c.Cout * 16.0 * (e / 2) * (e / 2)
-                                   : 2.0 * c.Cout * (double)c.Cin_real * c.nsrc * c.k * c.k * e * e);
+    fl += c.flops(cfg.batch);
   }
   label = cc[0].layer + (ng > 1 ? " (x" + std::to_string(ng) + ")" : "");
   if (c0.tz)
@@ -565,352 +598,344 @@ int cfen_net::run_conv_g(int ng, const ConvCall* cc, int act) {
   return CFEN_OK;
 }
 
+// The conditions in their order of precedence: dummy probe, GViT on the stream kernels, persistent chain, window kernel, then front and back half.
+VitRoute cfen_net::route(const Vit& v, int ng, int M, bool skip_up) const {
+  const int dt = cfg.dtype, dl = cfen_tune_gvit_dummy_levels(), gs = cfen_tune_gvit_stream(), ch = cfen_tune_gvit_chain();
+  const bool front3_ok = cfen_front3_supported(dt, v.D, (long long)M), hm_ok = cfen_attention_hm_supported(dt, v.S, v.D / v.heads);
+  const bool many = (long long)ng * M >= 128LL * 128;   // >= 128 workgroups of 128 tokens
+  VitRoute r;
+  r.upsample = v.global && !skip_up;
+  if (v.global && cfen_tune_gvit_dummy_wgs() != 0 && (dl == 0 || (!v.gstream && (dl == 1 || (dl == 2) == (v.D >= 1536))))) {   // levels: 1 = 2 and 3, 2 = level 3 only, 3 = level 2 only
+    r.whole = VitRoute::DUMMY;
+  } else if (v.gstream && (gs == 2 || (gs == 1 && !parallel)) && front3_ok) {
+    r.whole = VitRoute::GSTREAM;
+    r.front = VitRoute::FRONT3;
+    r.back = VitRoute::MLP3;
+  } else if (v.chain && (ch == 1 || ch == 4 || ch == 5 || (ch == 2 && ng > 1) || (ch == 3 && ng == 1))) {
+    r.whole = VitRoute::CHAIN;
+    r.team = std::max(1, std::min(cfen_tune_gvit_team(), 256 / (ng * std::max(1, cfen_tune_gvit_max_concurrent()))));   // every team of every forward in flight must be RESIDENT at once (grid barrier)
+    r.per_gemm = ch >= 4;
+    r.split_team = ch == 4 ? 0 : ch == 5 ? 256 / ng : r.team;
+  } else if (v.fused_window && cfen_tune_lvit_window()) {
+    r.whole = VitRoute::WINDOW;
+  }
+  if (r.whole != VitRoute::PARTS) return r;
+  if (v.stream_mlp && front3_ok && hm_ok && (cfen_tune_stream_front() >= 2 || (cfen_tune_stream_front() == 1 && many))) {
+    r.front = VitRoute::FRONT3;
+    r.head_major = true;
+  } else if (v.fused_front && v.D <= cfen_tune_fused_front_max_dim()) {
+    r.front = VitRoute::EMBED_QKV;
+    r.head_major = cfen_tune_attn_head_major() && hm_ok;
+  }
+  // D = 384: launches of >= 128 workgroups of 128 tokens; D = 192 (LViT level 2): always -- k_mlp3<12, 3> is spill-free and 192-token workgroups
+  // make the grouped decoder launch exactly two rounds (154-162 us against k_mlp2's 181-204, tools/bench_mlp3.py)
+  if (v.stream_mlp && (v.D == 192 ? cfen_tune_stream_mlp192() != 0 : (cfen_tune_stream_mlp() >= 2 || (cfen_tune_stream_mlp() == 1 && many))))
+    r.back = VitRoute::MLP3;
+  else if (v.fused_mlp)
+    r.back = VitRoute::MLP;
+  r.gather_in_gemm = !v.global && cfen_tune_embed_gather();
+  r.ln1_fold = v.ln_fold1 && cfen_tune_ln_fold();
+  r.ln2_fold = v.ln_fold2 && cfen_tune_ln_fold();
+  r.fold_in_gemm = cfen_tune_fold_in_gemm() != 0;
+  return r;
+}
+
+// Per-call operands of one block group (member g: scratch set scr0 + 2 g, parameters of instance nm[g]), built once at the top of run_vit_g, and one builder per argument struct
+struct cfen_net::VitCtx {
+  cfen_net& n;
+  const Vit& v;
+  const Buf &bi, &bo;
+  const int ng, dt, B, nwin, M, dst_cs;
+  void *X0[3], *X1[3], *YN[3], *QKV[3], *ATT[3], *HID[3], *OUT[3];
+  void* DST[3];   // where the block's folded result goes, at channel stride dst_cs: GViT -> the `small` map of the scratch set at v.C (x4 bilinear follows), LViT -> the output map at bo.cs
+  const void* IN[3];
+  float* SK[3] = {nullptr, nullptr, nullptr};   // split-K scratch of each member (GViT: few tokens against 0.5 GB of weights per forward)
+  unsigned* SYNC[3] = {nullptr, nullptr, nullptr};   // ... and its barrier / error words
+  std::string nm[3];
+  const double Md, D, Hd, DD, DH;   // algorithmic flops count the real embedding dim (D = v.Dn); DD, DH: weight elements of a D x D / D x hidden matrix
+
+  VitCtx(cfen_net& net, int ng_, const VitCall* vc, int scr0)
+      : n(net), v(*vc[0].v), bi(net.bufs.at(vc[0].in)), bo(net.bufs.at(vc[0].out)), ng(ng_), dt(net.cfg.dtype), B(net.cfg.batch),
+        nwin((v.mapH / v.ws) * (v.mapH / v.ws)), M(B * nwin * v.S), dst_cs(v.global ? v.C : bo.cs), Md((double)M * ng), D(v.Dn), Hd(v.hidden),
+        DD((double)v.D * v.D), DH((double)v.D * v.hidden) {
+    for (int g = 0; g < ng; ++g) {
+      const Scratch& q = n.scr_set[scr0 + 2 * g];
+      X0[g] = n.at(q.x0); X1[g] = n.at(q.x1); YN[g] = n.at(q.yn); QKV[g] = n.at(q.qkv); ATT[g] = n.at(q.att); HID[g] = n.at(q.hid);
+      if (v.global) { SK[g] = (float*)n.at(q.splitk); SYNC[g] = (unsigned*)n.at(q.sync); }
+      IN[g] = n.map_ptr(vc[g].in); OUT[g] = n.map_ptr(vc[g].out);
+      DST[g] = v.global ? n.at(q.small) : OUT[g];
+      nm[g] = vc[g].v->name;
+    }
+  }
+  const void* P(int g, const char* s, const char* sfx = "") const { return n.P(nm[g] + s + sfx); }   // parameter "<name><s><sfx>" of member g
+  const float* Pf(int g, const char* s, const char* sfx = "") const { return (const float*)P(g, s, sfx); }
+  void step(const char* what) const { if (n.profiling) n.label = nm[0] + (ng > 1 ? " (x" + std::to_string(ng) + ")" : "") + ":" + what; }
+  // algorithmic bytes of a token GEMM launch: weights once + tokens in + tokens out (SURVEY 8d: what a weight-streaming GEMM is priced against)
+  void gemm_bytes(int N, int K) const { n.prof_bytes = (double)ng * ((double)N * K + (double)M * K + (double)M * N) * n.esz; }
+  // ... of a fused token-block launch (round 6: priced for the MFMA-bound kernels too, so that counter traffic / algorithmic bytes can be read from the bench line):
+  // `rows` token-row-sized tensors in and out (M x D elements each: map or token reads, X1 / QKV / ATT / map writes) + `welems` weight elements read once
+  void block_bytes(double rows, double welems) const { n.prof_bytes = (double)ng * (rows * (double)M * v.D + welems) * n.esz; }
+  double fl_front() const { return 8 * Md * D * D; }                     // embed + qkv (integers below 2^53, like ConvLayer::flops)
+  double fl_attn() const { return 4 * Md * v.S * D; }
+  double fl_back() const { return 8 * Md * D * Hd + 2 * Md * D * D; }    // FFN + mlp_head, out_proj
+
+  int gemm(const VitGemm& a) const {
+    CfenGemmPtrs gp[3];
+    for (int g = 0; g < ng; ++g)
+      gp[g] = CfenGemmPtrs{a.tg ? nullptr : a.X[g], P(g, a.w), a.bias ? Pf(g, a.bias) : nullptr, a.R ? a.R[g] : nullptr, a.pos ? P(g, a.pos) : nullptr, a.Y[g],
+                           a.tg ? IN[g] : nullptr, a.lnf_s ? Pf(g, a.lnf_s) : nullptr, v.global && n.wtile, a.fold ? DST[g] : nullptr};
+    const CfenTokGather yg{nullptr, B, v.mapH, v.mapH, v.C, dst_cs, v.ws, v.p};
+    return cfen_gemm_impl_g(dt, ng, gp, a.K, a.K, a.N, v.S, a.N, M, a.N, a.K, a.relu, a.tg, n.stream, v.global ? SK : nullptr, v.global ? SPLITK_BYTES : 0,
+                            a.fold ? &yg : nullptr);
+  }
+  int layernorm(const char* lname) const {   // YN = LayerNorm(X1)
+    const float *lg[3], *lb[3];
+    for (int g = 0; g < ng; ++g) { lg[g] = Pf(g, lname, ".g"); lb[g] = Pf(g, lname, ".b"); }
+    return cfen_layernorm_impl_g(dt, ng, X1, YN, lg, lb, M, v.D, 1e-5f, n.stream, v.Dn);
+  }
+  // fused front half: weights "<name>.embed<sfx>" / ".qkv<sfx>", patch tokens gathered from `src` at channel stride cs
+  CfenEmbedQkvArgs embed_qkv_args(int g, const char* sfx, const void* src, int cs, int hm_heads) const {
+    return CfenEmbedQkvArgs{src, B, v.mapH, v.mapH, v.C, cs, v.ws, v.p, P(g, ".embed", sfx), Pf(g, ".embed.b"), P(g, ".pos"),
+                            Pf(g, ".ln1.g"), Pf(g, ".ln1.b"), P(g, ".qkv", sfx), X1[g], QKV[g], M, v.D, 1e-5f, hm_heads};
+  }
+  template <class A> A mlp_common(int g, const char* wp) const {   // what Mlp3Args and MlpArgs share: everything but the MLP weights
+    A m{};
+    m.X = X1[g]; m.Y = nullptr; m.fmap = DST[g];
+    m.A = ATT[g]; m.Wp = P(g, wp);   // out_proj + residual ride on the kernel's token load
+    m.ln_g = Pf(g, ".ln2.g"); m.ln_b = Pf(g, ".ln2.b");
+    m.b1a = Pf(g, ".ffn1.b"); m.b2a = Pf(g, ".ffn2.b"); m.b1b = Pf(g, ".head1.b"); m.b2b = Pf(g, ".head2.b");
+    m.M = M; m.D = v.D; m.H = v.hidden; m.eps = 1e-5f;
+    m.mapH = v.mapH; m.mapW = v.mapH; m.C = v.C; m.cs = dst_cs; m.ws = v.ws; m.p = v.p;
+    return m;
+  }
+  Mlp3Args mlp3_args(int g) const {
+    Mlp3Args m = mlp_common<Mlp3Args>(g, ".proj.ws");
+    m.Wa = P(g, ".ffn.ws"); m.Wb = P(g, ".head.ws");
+    return m;
+  }
+  MlpArgs mlp_args(int g) const {
+    MlpArgs m = mlp_common<MlpArgs>(g, ".proj.w");
+    m.W1a = P(g, ".ffn1.wk"); m.W2a = P(g, ".ffn2.wk"); m.W1b = P(g, ".head1.wk"); m.W2b = P(g, ".head2.wk");
+    return m;
+  }
+  // one phase of a persistent chain: Y = act(X W^T + bias) + R + P on the fragment stream "<name><layer>.wf".  lnf: the LayerNorm of X is folded (bias ".bl",
+  // row sums ".s"); R is a token buffer of N = v.D columns; fold: Y is the map (CfenChainArgs::fH ...)
+  CfenChainPhase chain_phase(int g, const void* X, const char* layer, bool bias, bool lnf, const void* R, bool pos, void* Y, int N, int K, int relu,
+                             int nsplit, int fold = 0) const {
+    return CfenChainPhase{X, P(g, layer, ".wf"), lnf ? Pf(g, layer, ".bl") : bias ? Pf(g, layer, ".b") : nullptr, lnf ? Pf(g, layer, ".s") : nullptr, R,
+                          pos ? P(g, ".pos") : nullptr, Y, K, R ? N : 0, N, pos ? v.S : 0, N, K, relu, nsplit, fold};
+  }
+  // a chain launch of `nph` phases for member g: it takes barrier word n.gv_launch of the member's scratch set
+  int chain_args(int g, int nph, CfenChainArgs& c) const {
+    CFEN_CHECK_ARG(n.gv_launch < GV_ERR_WORD, "net: too many persistent-chain launches in one forward");
+    c = CfenChainArgs{};
+    c.nph = nph; c.M = M;
+    c.bar = SYNC[g] + n.gv_launch; c.err = SYNC[g] + GV_ERR_WORD;
+    c.cnt = (unsigned*)SK[g]; c.ncnt = CFEN_SPLITK_COUNTERS;
+    c.part = SK[g] + CFEN_SPLITK_COUNTERS * sizeof(unsigned) / sizeof(float); c.part_bytes = SPLITK_BYTES - CFEN_SPLITK_COUNTERS * sizeof(unsigned);
+    return CFEN_OK;
+  }
+};
+
+// one token GEMM launch of a block.  priced: the launch's algorithmic bytes go into the profile
+int cfen_net::vit_gemm(VitCtx& c, const char* what, bool priced, double fl, const VitGemm& a) {
+  c.step(what);
+  if (priced) c.gemm_bytes(a.N, a.K);
+  TRYP(K_GEMM, fl, c.gemm(a));
+  return CFEN_OK;
+}
+
+// Front half: gather + linear_encoding + residual + position + LN1 + qkv, map -> X1, QKV
+int cfen_net::vit_front(VitCtx& c, const VitRoute& r) {
+  const Vit& v = c.v;
+  const int dt = c.dt, ng = c.ng;
+  if (r.front != VitRoute::FRONT_GEMMS) {
+    // one launch: LViT level 3 on row-tile weight streams (k_stream.hip), levels 1-2 on k_embed.hip, x -> X1, QKV
+    const bool stream3 = r.front == VitRoute::FRONT3, pooled = r.whole == VitRoute::GSTREAM;
+    if (pooled) {   // the token scratch holds the pooled map: B x mapH x mapH x C = M x D elements
+      c.step("pool4");
+      TRYP(K_TOKEN, 0, cfen_pool4_impl_g(dt, ng, c.IN, c.X0, c.B, v.mapH, v.mapH, v.C, c.bi.cs, v.C, stream));
+    }
+    CfenEmbedQkvArgs e[3];
+    for (int g = 0; g < ng; ++g)
+      e[g] = c.embed_qkv_args(g, stream3 ? ".ws" : ".wk", pooled ? c.X0[g] : c.IN[g], pooled ? v.C : c.bi.cs, r.head_major ? v.heads : 0);
+    c.step(stream3 ? "front_stream" : "embed_ln_qkv");
+    c.block_bytes(5, 4 * c.DD);     // pixels in, X1 + q / k / v out; W_e + W_qkv
+    TRYP(K_GEMM, c.fl_front(), stream3 ? cfen_front3_impl_g(dt, ng, e, stream) : cfen_embed_qkv_impl_g(dt, ng, e, stream));
+    return CFEN_OK;
+  }
+  const double Md = c.Md, D = c.D;
+  // x = linear_encoding(x) + x + pos                                      (v3:1143,1166)
+  const CfenTokGather tg{nullptr, c.B, v.mapH, v.mapH, v.C, c.bi.cs, v.ws, v.p};
+  if (r.gather_in_gemm) {   // LViT: the window / patch gather rides on the embedding GEMM's loader, no token buffer is written
+    TRY(vit_gemm(c, "embed", false, 2 * Md * D * D, {nullptr, ".embed.w", ".embed.b", nullptr, ".pos", c.X1, v.D, v.D, 0, &tg}));
+  } else {
+    c.step("patchify");
+    TRYP(K_TOKEN, 0, cfen_patchify_impl_g(dt, ng, c.IN, c.X0, c.B, v.mapH, v.mapH, v.C, c.bi.cs, v.ws, v.p, v.global ? 4 : 1, 0, stream));
+    TRY(vit_gemm(c, "embed", true, 2 * Md * D * D, {c.X0, ".embed.w", ".embed.b", c.X0, ".pos", c.X1, v.D, v.D, 0}));
+  }
+  // src = src + out_proj(MHA(LN1(src)))                                      (v3:1383-1386)
+  if (r.ln1_fold)
+    return vit_gemm(c, "ln1_qkv", true, 6 * Md * D * D, {c.X1, ".qkv.wl", ".qkv.bl", nullptr, nullptr, c.QKV, 3 * v.Da, v.D, 0, nullptr, ".qkv.s"});
+  c.step("ln1");
+  TRYP(K_LNORM, 0, c.layernorm(".ln1"));
+  return vit_gemm(c, "qkv", false, 6 * Md * D * D, {c.YN, ".qkv.w", nullptr, nullptr, nullptr, c.QKV, 3 * v.Da, v.D, 0});
+}
+
+int cfen_net::vit_attention(VitCtx& c, bool head_major) {
+  c.step("attention");
+  c.block_bytes(4, 0);   // q, k, v in; attention output out
+  TRYP(K_ATTN, c.fl_attn(), head_major ? cfen_attention_hm_impl_g(c.dt, c.ng, c.QKV, c.ATT, c.B * c.nwin, c.v.S, c.v.heads, c.v.D / c.v.heads, stream)
+                                       : cfen_attention_impl_g(c.dt, c.ng, c.QKV, c.ATT, c.B * c.nwin, c.v.S, c.v.heads, c.v.dh, stream));
+  return CFEN_OK;
+}
+
+// Back half: out_proj + residual + LN2 + FFN + mlp_head + fold, X1, ATT -> the map DST
+int cfen_net::vit_back(VitCtx& c, const VitRoute& r) {
+  const Vit& v = c.v;
+  const int dt = c.dt, ng = c.ng;
+  if (r.back != VitRoute::BACK_GEMMS) {
+    // one launch: on fragment-stream weights (k_stream.hip: LViT levels 3 and 2, GViT level 1), or k_mlp.hip: LN2 + FFN + residual + mlp_head + residual +
+    // fold, hidden activations never leave registers
+    const bool stream3 = r.back == VitRoute::MLP3;
+    Mlp3Args m3[3];
+    MlpArgs m[3];
+    for (int g = 0; g < ng; ++g) {
+      if (stream3)
+        m3[g] = c.mlp3_args(g);
+      else
+        m[g] = c.mlp_args(g);
+    }
+    c.step(stream3 ? "proj_mlp_stream" : "proj_mlp_fused");
+    c.block_bytes(3, c.DD + 4 * c.DH);   // X1 + attention output in, map out; W_p + the four MLP matrices
+    TRYP(K_MLP, c.fl_back(), stream3 ? cfen_mlp3_impl_g(dt, ng, m3, stream) : cfen_mlp_impl_g(dt, ng, m, stream));
+    return CFEN_OK;
+  }
+  const double Md = c.Md, D = c.D, Hd = c.Hd;
+  TRY(vit_gemm(c, "proj", true, 2 * Md * D * D, {c.ATT, ".proj.w", nullptr, c.X1, nullptr, c.X1, v.D, v.Da, 0}));
+  // src = src + linear2(relu(linear1(LN2(src))))                             (v3:1387-1389)
+  if (r.ln2_fold) {
+    TRY(vit_gemm(c, "ln2_ffn1", true, 2 * Md * D * Hd, {c.X1, ".ffn1.wl", ".ffn1.bl", nullptr, nullptr, c.HID, v.hidden, v.D, 1, nullptr, ".ffn1.s"}));
+  } else {
+    c.step("ln2");
+    TRYP(K_LNORM, 0, c.layernorm(".ln2"));
+    TRY(vit_gemm(c, "ffn1", false, 2 * Md * D * Hd, {c.YN, ".ffn1.w", ".ffn1.b", nullptr, nullptr, c.HID, v.hidden, v.D, 1}));
+  }
+  TRY(vit_gemm(c, "ffn2", true, 2 * Md * D * Hd, {c.HID, ".ffn2.w", ".ffn2.b", c.X1, nullptr, c.X1, v.D, v.hidden, 0}));
+  // x = mlp_head(x) + x                                                      (v3:1173)
+  TRY(vit_gemm(c, "head1", true, 2 * Md * D * Hd, {c.X1, ".head1.w", ".head1.b", nullptr, nullptr, c.HID, v.hidden, v.D, 1}));
+  if (r.fold_in_gemm)   // folded: the GEMM's epilogue writes feature (i, j, c) of token m to its pixel of the map   (v3:1173, 1186)
+    return vit_gemm(c, "head2_fold", true, 2 * Md * D * Hd, {c.HID, ".head2.w", ".head2.b", c.X1, nullptr, c.X0, v.D, v.hidden, 0, nullptr, nullptr, true});
+  TRY(vit_gemm(c, "head2", false, 2 * Md * D * Hd, {c.HID, ".head2.w", ".head2.b", c.X1, nullptr, c.X0, v.D, v.hidden, 0}));
+  c.step("fold");
+  TRYP(K_TOKEN, 0, cfen_patchify_impl_g(dt, ng, c.DST, c.X0, c.B, v.mapH, v.mapH, v.C, c.dst_cs, v.ws, v.p, 1, 1, stream));
+  return CFEN_OK;
+}
+
+// LViT level 1: one workgroup per window, embed -> attention -> MLP -> fold with q / k / v / attention output on chip (k_lvit.hip)
+int cfen_net::vit_window(VitCtx& c) {
+  const Vit& v = c.v;
+  LvitArgs w[3];
+  for (int g = 0; g < c.ng; ++g)
+    w[g] = LvitArgs{c.IN[g], c.OUT[g], c.B, v.mapH, v.mapH, v.C, c.bi.cs, c.bo.cs, v.ws, v.p, c.P(g, ".lw.ws"), c.Pf(g, ".embed.b"), c.P(g, ".pos"),
+                    c.Pf(g, ".ln1.g"), c.Pf(g, ".ln1.b"), c.Pf(g, ".ln2.g"), c.Pf(g, ".ln2.b"), c.Pf(g, ".ffn1.b"), c.Pf(g, ".ffn2.b"),
+                    c.Pf(g, ".head1.b"), c.Pf(g, ".head2.b"), v.hidden, 1e-5f, 1.4426950408889634f / sqrtf((float)(v.D / v.heads))};
+  c.step("window_block_fused");
+  c.block_bytes(2, 5 * c.DD + 4 * c.DH);   // map in, map out; W_e, W_qkv, W_p + the four MLP matrices
+  TRYP(K_MLP, c.fl_front() + c.fl_attn() + c.fl_back(), cfen_lvit_window_impl_g(c.dt, c.ng, w, stream));
+  return CFEN_OK;
+}
+
+// GViT block: pooled patch tokens -> [embed -> qkv] -> attention -> [proj -> ffn1 -> ffn2 -> head1 -> head2 + fold] -> x4 bilinear; the two
+// bracketed runs are ONE persistent launch each (k_gvit.hip): a team of workgroups per block keeps its CUs over the whole run
+int cfen_net::vit_chain(VitCtx& c, const VitRoute& r) {
+  const Vit& v = c.v;
+  const int ng = c.ng, D = v.D, H = v.hidden;
+  auto nsp = [&](int N, int K) {   // K slices so that the phase has work for most of the team (>= 4 K-steps of 64 per slice)
+    int n = 1;
+    const int units = ((c.M + 127) / 128) * (N / 128);
+    while (units * n * 2 <= r.split_team && n < 8 && (K / 64) % (2 * n) == 0 && K / 64 / (2 * n) >= 4) n *= 2;
+    return n;
+  };
+  CfenChainArgs ca[3];
+  auto run_chain = [&](const char* what, double fl) -> int {   // one chain stage: a persistent launch of all its phases, or a launch per phase
+    const int nph = ca[0].nph;
+    if (!r.per_gemm) {
+      c.step(what);
+      TRYP(K_GEMM, fl, cfen_gvit_chain_impl_g(c.dt, ng, ca, r.team, stream));
+      return CFEN_OK;
+    }
+    for (int p = 0; p < nph; ++p) {
+      CfenChainArgs one[3];
+      for (int g = 0; g < ng; ++g) {
+        one[g] = ca[g];
+        one[g].ph[0] = ca[g].ph[p];
+        one[g].nph = 1;
+      }
+      const int units = ((c.M + 127) / 128) * (one[0].ph[0].N / 128) * std::max(1, one[0].ph[0].nsplit);
+      c.step((std::string(what) + "." + std::to_string(p)).c_str());
+      // (no grid barrier in a one-phase launch: the residency cap of the persistent chains does not apply)
+      TRYP(K_GEMM, fl / nph, cfen_gvit_chain_impl_g(c.dt, ng, one, std::min(256 / ng, units), stream));
+    }
+    return CFEN_OK;
+  };
+  c.step("patchify");
+  TRYP(K_TOKEN, 0, cfen_patchify_impl_g(c.dt, ng, c.IN, c.X0, c.B, v.mapH, v.mapH, v.C, c.bi.cs, v.ws, v.p, 4, 0, stream));
+  for (int g = 0; g < ng; ++g) {
+    TRY(c.chain_args(g, 2, ca[g]));
+    //                             X         layer     bias   lnf    R        pos    Y          N      K  relu nsplit
+    ca[g].ph[0] = c.chain_phase(g, c.X0[g], ".embed", true,  false, c.X0[g], true,  c.X1[g],   D,     D, 0,   nsp(D, D));
+    ca[g].ph[1] = c.chain_phase(g, c.X1[g], ".qkv",   true,  true,  nullptr, false, c.QKV[g],  3 * D, D, 0,   1);
+  }
+  ++gv_launch;   // once per chain stage, after every member took its barrier word
+  TRY(run_chain("chain_embed_qkv", c.fl_front()));
+  TRY(vit_attention(c, false));
+  for (int g = 0; g < ng; ++g) {
+    TRY(c.chain_args(g, 5, ca[g]));
+    ca[g].fH = v.mapH; ca[g].fW = v.mapH; ca[g].fcs = v.C; ca[g].fC = v.C; ca[g].fp = v.p;
+    ca[g].ph[0] = c.chain_phase(g, c.ATT[g], ".proj",  false, false, c.X1[g], false, c.X1[g],  D,     D, 0,   nsp(D, D));
+    ca[g].ph[1] = c.chain_phase(g, c.X1[g],  ".ffn1",  true,  true,  nullptr, false, c.HID[g], H,     D, 1,   1);
+    ca[g].ph[2] = c.chain_phase(g, c.HID[g], ".ffn2",  true,  false, c.X1[g], false, c.X1[g],  D,     H, 0,   nsp(D, H));
+    ca[g].ph[3] = c.chain_phase(g, c.X1[g],  ".head1", true,  false, nullptr, false, c.HID[g], H,     D, 1,   1);
+    ca[g].ph[4] = c.chain_phase(g, c.HID[g], ".head2", true,  false, c.X1[g], false, c.DST[g], D,     H, 0,   nsp(D, H), 1);
+  }
+  ++gv_launch;
+  return run_chain("chain_proj_mlp_head", c.fl_back());
+}
+
 // One LViT / GViT instance: reference v3:1136-1189 / 1272-1325 (+ TransformerEncoderLayer 1382-1390).
-int cfen_net::run_vit_g(int ng, const VitCall* vc, int scr0) {
-  const int dt = cfg.dtype, B = cfg.batch;
+int cfen_net::run_vit_g(int ng, const VitCall* vc, int scr0, bool skip_up) {
   const Vit& v = *vc[0].v;
-  const Buf& bi = bufs.at(vc[0].in);
-  const Buf& bo = bufs.at(vc[0].out);
-  const int nwin = (v.mapH / v.ws) * (v.mapH / v.ws);
-  const int M = B * nwin * v.S;
   blk_kind = v.global ? 1 : 2;
   struct Reset { int& k; ~Reset() { k = 0; } } reset_{blk_kind};
   CFEN_CHECK_ARG(v.global == (bool)(scr0 & 1) && scr0 + 2 * (ng - 1) < 6, "net: %s enqueued on the wrong scratch set", v.name.c_str());
-  // per-member operands: scratch set scr0 + 2g, parameters by instance name
-  void *X0[3], *X1[3], *YN[3], *QKV[3], *ATT[3], *HID[3], *SM[3], *OUT[3];
-  const void *IN[3], *cX0[3], *cX1[3], *cYN[3], *cQKV[3], *cSM[3];
-  std::string nm[3];
   for (int g = 0; g < ng; ++g) {
     const Vit& w = *vc[g].v;
     CFEN_CHECK_ARG(w.global == v.global && w.D == v.D && w.Dn == v.Dn && w.Da == v.Da && w.hidden == v.hidden && w.S == v.S && w.mapH == v.mapH && w.heads == v.heads &&
-                   w.fused_mlp == v.fused_mlp && w.fused_front == v.fused_front && bufs.at(vc[g].in).cs == bi.cs && bufs.at(vc[g].out).cs == bo.cs,
-                   "net: %s and %s cannot share launches", v.name.c_str(), w.name.c_str());
-    const Scratch& q = scr_set[scr0 + 2 * g];
-    X0[g] = at(q.x0); X1[g] = at(q.x1); YN[g] = at(q.yn); QKV[g] = at(q.qkv); ATT[g] = at(q.att); HID[g] = at(q.hid);
-    SM[g] = v.global ? at(q.small) : nullptr;
-    IN[g] = map_ptr(vc[g].in); OUT[g] = map_ptr(vc[g].out);
-    cX0[g] = X0[g]; cX1[g] = X1[g]; cYN[g] = YN[g]; cQKV[g] = QKV[g]; cSM[g] = SM[g];
-    nm[g] = w.name;
+                   w.fused_mlp == v.fused_mlp && w.fused_front == v.fused_front && bufs.at(vc[g].in).cs == bufs.at(vc[0].in).cs &&
+                   bufs.at(vc[g].out).cs == bufs.at(vc[0].out).cs, "net: %s and %s cannot share launches", v.name.c_str(), w.name.c_str());
   }
-  const void* cHIDp[3] = {HID[0], HID[1], HID[2]};
-  float* SK[3] = {nullptr, nullptr, nullptr};   // split-K scratch of each member (GViT: few tokens against 0.5 GB of weights per forward)
-  if (v.global)
-    for (int g = 0; g < ng; ++g) SK[g] = (float*)at(scr_set[scr0 + 2 * g].splitk);
-  const double Md = (double)M * ng, D = v.Dn, Hd = v.hidden;   // algorithmic flops count the real embedding dim
-  auto step = [&](const char* what) { if (profiling) label = nm[0] + (ng > 1 ? " (x" + std::to_string(ng) + ")" : "") + ":" + what; };
+  VitCtx c(*this, ng, vc, scr0);
   for (int i = 0; i < cfen_tune_extra_launches(); ++i) {
-    step("extra_launch");
-    TRY(cfen_occupy_impl(-1, 1, 1, 0, base, ws_bytes, X0[0], stream));
+    c.step("extra_launch");
+    TRY(cfen_occupy_impl(-1, 1, 1, 0, base, ws_bytes, c.X0[0], stream));
   }
-  if (v.global && cfen_tune_gvit_dummy_wgs() != 0 && (cfen_tune_gvit_dummy_levels() == 0 || (!v.gstream && (cfen_tune_gvit_dummy_levels() == 1 || (cfen_tune_gvit_dummy_levels() == 2) == (v.D >= 1536))))) {   // levels: 1 = 2 and 3, 2 = level 3 only, 3 = level 2 only   // what-if probe: the whole block replaced by a launch that holds CUs (outputs invalid)
-    step("dummy");
-    return cfen_occupy_impl(cfen_tune_gvit_dummy_wgs(), ng, cfen_tune_gvit_dummy_us(), cfen_tune_gvit_dummy_stream(), base, ws_bytes, SK[0], stream);
+  const VitRoute r = route(v, ng, c.M, skip_up);
+  switch (r.whole) {
+    case VitRoute::DUMMY:   // what-if probe: the whole block replaced by a launch that holds CUs (outputs invalid)
+      c.step("dummy");
+      return cfen_occupy_impl(cfen_tune_gvit_dummy_wgs(), ng, cfen_tune_gvit_dummy_us(), cfen_tune_gvit_dummy_stream(), base, ws_bytes, c.SK[0], stream);
+    case VitRoute::WINDOW: TRY(vit_window(c)); break;
+    case VitRoute::CHAIN: TRY(vit_chain(c, r)); break;
+    case VitRoute::GSTREAM:
+    case VitRoute::PARTS:
+      TRY(vit_front(c, r));
+      TRY(vit_attention(c, r.head_major));
+      TRY(vit_back(c, r));
   }
-  // Y = act(X W^T + bias) + R + P for every member; operand arrays are indexed by member
-  auto gemm = [&](const void* const* X, const char* wname, const char* bname, void* const* R, const char* pname, void* const* Y, int N, int K,
-                  int relu, const CfenTokGather* tg) -> int {
-    CfenGemmPtrs gp[3];
-    for (int g = 0; g < ng; ++g)
-      gp[g] = CfenGemmPtrs{tg ? nullptr : X[g], P(nm[g] + wname), bname ? Pf(nm[g] + bname) : nullptr, R ? R[g] : nullptr,
-                           pname ? P(nm[g] + pname) : nullptr, Y[g], tg ? IN[g] : nullptr, nullptr, v.global && wtile};
-    return cfen_gemm_impl_g(dt, ng, gp, K, K, N, v.S, N, M, N, K, relu, tg, stream, v.global ? SK : nullptr, v.global ? SPLITK_BYTES : 0);
-  };
-  // algorithmic bytes of a token GEMM launch: weights once + tokens in + tokens out (SURVEY 8d: what a weight-streaming GEMM is priced against)
-  auto gemm_bytes = [&](int N, int K) { prof_bytes = (double)ng * ((double)N * K + (double)M * K + (double)M * N) * esz; };
-  // ... of a fused token-block launch (round 6: priced for the MFMA-bound kernels too, so that counter traffic / algorithmic bytes can be read from the bench line):
-  // `rows` token-row-sized tensors in and out (M x D elements each: map or token reads, X1 / QKV / ATT / map writes) + `welems` weight elements read once
-  auto block_bytes = [&](double rows, double welems) { prof_bytes = (double)ng * (rows * (double)M * v.D + welems) * esz; };
-  const double DD = (double)v.D * v.D, DH = (double)v.D * v.hidden;
-  // Y = act(LN(X) W0^T + b0) with the LayerNorm folded: parameters `lname`.wl / .s / .bl (packing.ln_folded)
-  auto gemm_ln = [&](const void* const* X, const std::string& lname, void* const* Y, int N, int K, int relu) -> int {
-    CfenGemmPtrs gp[3];
-    for (int g = 0; g < ng; ++g)
-      gp[g] = CfenGemmPtrs{X[g], P(nm[g] + lname + ".wl"), Pf(nm[g] + lname + ".bl"), nullptr, nullptr, Y[g], nullptr, Pf(nm[g] + lname + ".s"),
-                           v.global && wtile};
-    return cfen_gemm_impl_g(dt, ng, gp, K, K, N, v.S, N, M, N, K, relu, nullptr, stream, v.global ? SK : nullptr, v.global ? SPLITK_BYTES : 0);
-  };
-  if (v.gstream && (cfen_tune_gvit_stream() == 2 || (cfen_tune_gvit_stream() == 1 && !parallel)) && cfen_front3_supported(dt, v.D, (long long)M)) {
-    // GViT block of embedding dim 384 (level 1) on the LViT-3 stream kernels: 4 x 4 pooled MAP -> k_front3 (patch gather + linear_encoding + residual +
-    // position + LN1 + in_proj, qkv row-major) -> attention -> k_mlp3 (out_proj + LN2 + FFN + mlp_head + fold into the pooled-size map) -> x4
-    // bilinear: 5 launches instead of 10, and the two stream launches are 16 whole-CU workgroups per block -- 2-3x the latency of the GEMM chain and
-    // a fraction of its CU-time, which is what counts with several forwards in flight
-    const void* PM[3];
-    for (int g = 0; g < ng; ++g) PM[g] = X0[g];          // the token scratch holds the pooled map: B x mapH x mapH x C = M x D elements
-    step("pool4");
-    TRYP(K_TOKEN, 0, cfen_pool4_impl_g(dt, ng, IN, X0, B, v.mapH, v.mapH, v.C, bi.cs, v.C, stream));
-    CfenEmbedQkvArgs e[3];
-    for (int g = 0; g < ng; ++g)
-      e[g] = CfenEmbedQkvArgs{PM[g], B, v.mapH, v.mapH, v.C, v.C, v.ws, v.p, P(nm[g] + ".embed.ws"), Pf(nm[g] + ".embed.b"), P(nm[g] + ".pos"),
-                              Pf(nm[g] + ".ln1.g"), Pf(nm[g] + ".ln1.b"), P(nm[g] + ".qkv.ws"), X1[g], QKV[g], M, v.D, 1e-5f, 0};
-    step("front_stream");
-    block_bytes(5, 4 * DD);     // pixels in, X1 + q / k / v out; W_e + W_qkv
-    TRYP(K_GEMM, 8 * Md * D * D, cfen_front3_impl_g(dt, ng, e, stream));
-    step("attention");
-    block_bytes(4, 0);   // q, k, v in; attention output out
-    TRYP(K_ATTN, 4 * Md * v.S * D, cfen_attention_impl_g(dt, ng, cQKV, ATT, B * nwin, v.S, v.heads, v.dh, stream));
-    Mlp3Args m[3];
-    for (int g = 0; g < ng; ++g) {
-      const std::string& n = nm[g];
-      m[g] = Mlp3Args{};
-      m[g].X = X1[g]; m[g].A = ATT[g]; m[g].Wp = P(n + ".proj.ws"); m[g].Y = nullptr; m[g].fmap = SM[g];
-      m[g].ln_g = Pf(n + ".ln2.g"); m[g].ln_b = Pf(n + ".ln2.b");
-      m[g].Wa = P(n + ".ffn.ws"); m[g].b1a = Pf(n + ".ffn1.b"); m[g].b2a = Pf(n + ".ffn2.b");
-      m[g].Wb = P(n + ".head.ws"); m[g].b1b = Pf(n + ".head1.b"); m[g].b2b = Pf(n + ".head2.b");
-      m[g].M = M; m[g].D = v.D; m[g].H = v.hidden; m[g].eps = 1e-5f;
-      m[g].mapH = v.mapH; m[g].mapW = v.mapH; m[g].C = v.C; m[g].cs = v.C; m[g].ws = v.ws; m[g].p = v.p;
-    }
-    step("proj_mlp_stream");
-    block_bytes(3, DD + 4 * DH);   // X1 + attention output in, map out; W_p + the four MLP matrices
-    TRYP(K_MLP, 8 * Md * D * Hd + 2 * Md * D * D, cfen_mlp3_impl_g(dt, ng, m, stream));
-    if (gv_skip_up) return CFEN_OK;
-    step("upsample4");
-    TRYP(K_TOKEN, 0, cfen_upsample4_impl_g(dt, ng, cSM, OUT, B, v.mapH, v.mapH, v.C, v.C, bo.cs, stream));
-    return CFEN_OK;
-  }
-  if (v.chain && (cfen_tune_gvit_chain() == 1 || cfen_tune_gvit_chain() == 4 || cfen_tune_gvit_chain() == 5 || (cfen_tune_gvit_chain() == 2 && ng > 1) || (cfen_tune_gvit_chain() == 3 && ng == 1))) {
-    // GViT block: pooled patch tokens -> [embed -> qkv] -> attention -> [proj -> ffn1 -> ffn2 -> head1 -> head2 + fold] -> x4 bilinear; the two
-    // bracketed runs are ONE persistent launch each (k_gvit.hip): a team of workgroups per block keeps its CUs over the whole run
-    const int team = std::max(1, std::min(cfen_tune_gvit_team(), 256 / (ng * std::max(1, cfen_tune_gvit_max_concurrent()))));   // every team of every forward in flight must be RESIDENT at once (grid barrier)
-    const bool per_gemm = cfen_tune_gvit_chain() >= 4;   // 4: every GEMM its own launch of the chain kernel, never split over K: no grid barrier, no split-K seam;
-                                                         // 5 (round 5 A/B): as 4 with K split so that a launch has ~a workgroup per CU (in-launch split-K seam, no grid barrier)
-    const int split_team = cfen_tune_gvit_chain() == 5 ? 256 / ng : team;
-    auto nsp = [&](int N, int K) {   // K slices so that the phase has work for most of the team (>= 4 K-steps of 64 per slice)
-      int n = 1;
-      if (cfen_tune_gvit_chain() == 4) return n;
-      const int units = ((M + 127) / 128) * (N / 128);
-      while (units * n * 2 <= split_team && n < 8 && (K / 64) % (2 * n) == 0 && K / 64 / (2 * n) >= 4) n *= 2;
-      return n;
-    };
-    auto sync_of = [&](int g, CfenChainArgs& c) {
-      unsigned* w = (unsigned*)at(scr_set[scr0 + 2 * g].sync);
-      CFEN_CHECK_ARG(gv_launch < GV_ERR_WORD, "net: too many persistent-chain launches in one forward");
-      c.bar = w + gv_launch; c.err = w + GV_ERR_WORD;
-      c.cnt = (unsigned*)SK[g]; c.ncnt = CFEN_SPLITK_COUNTERS;
-      c.part = SK[g] + CFEN_SPLITK_COUNTERS * sizeof(unsigned) / sizeof(float); c.part_bytes = SPLITK_BYTES - CFEN_SPLITK_COUNTERS * sizeof(unsigned);
-      return CFEN_OK;
-    };
-    step("patchify");
-    TRYP(K_TOKEN, 0, cfen_patchify_impl_g(dt, ng, IN, X0, B, v.mapH, v.mapH, v.C, bi.cs, v.ws, v.p, 4, 0, stream));
-    CfenChainArgs ca[3];
-    for (int g = 0; g < ng; ++g) {
-      const std::string& n = nm[g];
-      CfenChainArgs& c = ca[g];
-      c = CfenChainArgs{};
-      c.nph = 2; c.M = M;
-      //                      X       W                  bias                 lnf_s              R       P             Y       ldx   ldr   ldy     period N       K    relu nsplit fold
-      c.ph[0] = CfenChainPhase{X0[g], P(n + ".embed.wf"), Pf(n + ".embed.b"), nullptr, X0[g], P(n + ".pos"), X1[g], v.D, v.D, v.D, v.S, v.D, v.D, 0, nsp(v.D, v.D), 0};
-      c.ph[1] = CfenChainPhase{X1[g], P(n + ".qkv.wf"), Pf(n + ".qkv.bl"), Pf(n + ".qkv.s"), nullptr, nullptr, QKV[g], v.D, 0, 3 * v.D, 0, 3 * v.D, v.D, 0, 1, 0};
-      TRY(sync_of(g, c));
-    }
-    ++gv_launch;
-    auto run_chain = [&](const char* what, double fl) -> int {
-      if (!per_gemm) {
-        step(what);
-        TRYP(K_GEMM, fl, cfen_gvit_chain_impl_g(dt, ng, ca, team, stream));
-        return CFEN_OK;
-      }
-      const int nph = ca[0].nph;
-      for (int p = 0; p < nph; ++p) {
-        CfenChainArgs one[3];
-        for (int g = 0; g < ng; ++g) {
-          one[g] = ca[g];
-          one[g].ph[0] = ca[g].ph[p];
-          one[g].nph = 1;
-        }
-        const int units = ((M + 127) / 128) * (one[0].ph[0].N / 128) * std::max(1, one[0].ph[0].nsplit);
-        const std::string lab = std::string(what) + "." + std::to_string(p);
-        step(lab.c_str());
-        // (no grid barrier in a one-phase launch: the residency cap of the persistent chains does not apply)
-        TRYP(K_GEMM, fl / nph, cfen_gvit_chain_impl_g(dt, ng, one, std::min(256 / ng, units), stream));
-      }
-      return CFEN_OK;
-    };
-    TRY(run_chain("chain_embed_qkv", 8 * Md * D * D));
-    step("attention");
-    block_bytes(4, 0);   // q, k, v in; attention output out
-    TRYP(K_ATTN, 4 * Md * v.S * D, cfen_attention_impl_g(dt, ng, cQKV, ATT, B * nwin, v.S, v.heads, v.dh, stream));
-    for (int g = 0; g < ng; ++g) {
-      const std::string& n = nm[g];
-      CfenChainArgs& c = ca[g];
-      c = CfenChainArgs{};
-      c.nph = 5; c.M = M;
-      c.fH = v.mapH; c.fW = v.mapH; c.fcs = v.C; c.fC = v.C; c.fp = v.p;
-      c.ph[0] = CfenChainPhase{ATT[g], P(n + ".proj.wf"), nullptr, nullptr, X1[g], nullptr, X1[g], v.D, v.D, v.D, 0, v.D, v.D, 0, nsp(v.D, v.D), 0};
-      c.ph[1] = CfenChainPhase{X1[g], P(n + ".ffn1.wf"), Pf(n + ".ffn1.bl"), Pf(n + ".ffn1.s"), nullptr, nullptr, HID[g], v.D, 0, v.hidden, 0, v.hidden, v.D, 1, 1, 0};
-      c.ph[2] = CfenChainPhase{HID[g], P(n + ".ffn2.wf"), Pf(n + ".ffn2.b"), nullptr, X1[g], nullptr, X1[g], v.hidden, v.D, v.D, 0, v.D, v.hidden, 0, nsp(v.D, v.hidden), 0};
-      c.ph[3] = CfenChainPhase{X1[g], P(n + ".head1.wf"), Pf(n + ".head1.b"), nullptr, nullptr, nullptr, HID[g], v.D, 0, v.hidden, 0, v.hidden, v.D, 1, 1, 0};
-      c.ph[4] = CfenChainPhase{HID[g], P(n + ".head2.wf"), Pf(n + ".head2.b"), nullptr, X1[g], nullptr, SM[g], v.hidden, v.D, v.D, 0, v.D, v.hidden, 0, nsp(v.D, v.hidden), 1};
-      TRY(sync_of(g, c));
-    }
-    ++gv_launch;
-    TRY(run_chain("chain_proj_mlp_head", 2 * Md * D * D + 8 * Md * D * Hd));
-    if (gv_skip_up) return CFEN_OK;
-    step("upsample4");
-    TRYP(K_TOKEN, 0, cfen_upsample4_impl_g(dt, ng, cSM, OUT, B, v.mapH, v.mapH, v.C, v.C, bo.cs, stream));
-    return CFEN_OK;
-  }
-  if (v.fused_window && cfen_tune_lvit_window()) {
-    // LViT level 1: one workgroup per window, embed -> attention -> MLP -> fold with q / k / v / attention output on chip (k_lvit.hip)
-    LvitArgs w[3];
-    for (int g = 0; g < ng; ++g) {
-      const std::string& n = nm[g];
-      w[g] = LvitArgs{IN[g], OUT[g], B, v.mapH, v.mapH, v.C, bi.cs, bo.cs, v.ws, v.p, P(n + ".lw.ws"), Pf(n + ".embed.b"), P(n + ".pos"),
-                      Pf(n + ".ln1.g"), Pf(n + ".ln1.b"), Pf(n + ".ln2.g"), Pf(n + ".ln2.b"), Pf(n + ".ffn1.b"), Pf(n + ".ffn2.b"),
-                      Pf(n + ".head1.b"), Pf(n + ".head2.b"), v.hidden, 1e-5f, 1.4426950408889634f / sqrtf((float)(v.D / v.heads))};
-    }
-    step("window_block_fused");
-    block_bytes(2, 5 * DD + 4 * DH);   // map in, map out; W_e, W_qkv, W_p + the four MLP matrices
-    TRYP(K_MLP, 8 * Md * D * D + 4 * Md * v.S * D + 8 * Md * D * Hd + 2 * Md * D * D, cfen_lvit_window_impl_g(dt, ng, w, stream));
-    return CFEN_OK;
-  }
-  const float* lg[3];
-  const float* lb[3];
-  bool head_major = false;   // the fused front half writes qkv per (window, head) for k_attention_hm
-  const long long Mll = M;
-  if (v.stream_mlp && cfen_front3_supported(dt, v.D, Mll) && cfen_attention_hm_supported(dt, v.S, v.D / v.heads) &&
-      (cfen_tune_stream_front() >= 2 || (cfen_tune_stream_front() == 1 && (long long)ng * M >= 128LL * 128))) {   // >= 128 workgroups of 128 tokens
-    // LViT level 3: gather + linear_encoding + residual + position + LN1 + qkv in one launch on row-tile weight streams (k_stream.hip)
-    CfenEmbedQkvArgs e[3];
-    head_major = true;
-    for (int g = 0; g < ng; ++g)
-      e[g] = CfenEmbedQkvArgs{IN[g], B, v.mapH, v.mapH, v.C, bi.cs, v.ws, v.p, P(nm[g] + ".embed.ws"), Pf(nm[g] + ".embed.b"), P(nm[g] + ".pos"),
-                              Pf(nm[g] + ".ln1.g"), Pf(nm[g] + ".ln1.b"), P(nm[g] + ".qkv.ws"), X1[g], QKV[g], M, v.D, 1e-5f, v.heads};
-    step("front_stream");
-    block_bytes(5, 4 * DD);     // pixels in, X1 + q / k / v out; W_e + W_qkv
-    TRYP(K_GEMM, 8 * Md * D * D, cfen_front3_impl_g(dt, ng, e, stream));
-  } else if (v.fused_front && v.D <= cfen_tune_fused_front_max_dim()) {
-    // LViT levels 1-2: gather + linear_encoding + residual + position + LN1 + qkv in one launch, x -> X1, QKV (k_embed.hip)
-    CfenEmbedQkvArgs e[3];
-    head_major = cfen_tune_attn_head_major() && cfen_attention_hm_supported(dt, v.S, v.D / v.heads);
-    for (int g = 0; g < ng; ++g)
-      e[g] = CfenEmbedQkvArgs{IN[g], B, v.mapH, v.mapH, v.C, bi.cs, v.ws, v.p, P(nm[g] + ".embed.wk"), Pf(nm[g] + ".embed.b"), P(nm[g] + ".pos"),
-                              Pf(nm[g] + ".ln1.g"), Pf(nm[g] + ".ln1.b"), P(nm[g] + ".qkv.wk"), X1[g], QKV[g], M, v.D, 1e-5f,
-                              head_major ? v.heads : 0};
-    step("embed_ln_qkv");
-    block_bytes(5, 4 * DD);
-    TRYP(K_GEMM, 8 * Md * D * D, cfen_embed_qkv_impl_g(dt, ng, e, stream));
-  } else {
-    if (v.global || !cfen_tune_embed_gather()) {
-      step("patchify");
-      TRYP(K_TOKEN, 0, cfen_patchify_impl_g(dt, ng, IN, X0, B, v.mapH, v.mapH, v.C, bi.cs, v.ws, v.p, v.global ? 4 : 1, 0, stream));
-      // x = linear_encoding(x) + x + pos                                      (v3:1143,1166)
-      step("embed");
-      gemm_bytes(v.D, v.D);
-      TRYP(K_GEMM, 2 * Md * D * D, gemm(cX0, ".embed.w", ".embed.b", X0, ".pos", X1, v.D, v.D, 0, nullptr));
-    } else {
-      // LViT: the window / patch gather rides on the embedding GEMM's loader, no token buffer is written
-      step("embed");
-      CfenTokGather tg{nullptr, B, v.mapH, v.mapH, v.C, bi.cs, v.ws, v.p};
-      TRYP(K_GEMM, 2 * Md * D * D, gemm(nullptr, ".embed.w", ".embed.b", nullptr, ".pos", X1, v.D, v.D, 0, &tg));
-    }
-    // src = src + out_proj(MHA(LN1(src)))                                      (v3:1383-1386)
-    if (v.ln_fold1 && cfen_tune_ln_fold()) {
-      step("ln1_qkv");
-      gemm_bytes(3 * v.Da, v.D);
-      TRYP(K_GEMM, 6 * Md * D * D, gemm_ln(cX1, ".qkv", QKV, 3 * v.Da, v.D, 0));
-    } else {
-      step("ln1");
-      for (int g = 0; g < ng; ++g) { lg[g] = Pf(nm[g] + ".ln1.g"); lb[g] = Pf(nm[g] + ".ln1.b"); }
-      TRYP(K_LNORM, 0, cfen_layernorm_impl_g(dt, ng, cX1, YN, lg, lb, M, v.D, 1e-5f, stream, v.Dn));
-      step("qkv");
-      TRYP(K_GEMM, 6 * Md * D * D, gemm(cYN, ".qkv.w", nullptr, nullptr, nullptr, QKV, 3 * v.Da, v.D, 0, nullptr));
-    }
-  }
-  step("attention");
-  block_bytes(4, 0);   // q, k, v in; attention output out
-  if (head_major)
-    TRYP(K_ATTN, 4 * Md * v.S * D, cfen_attention_hm_impl_g(dt, ng, cQKV, ATT, B * nwin, v.S, v.heads, v.D / v.heads, stream));
-  else
-    TRYP(K_ATTN, 4 * Md * v.S * D, cfen_attention_impl_g(dt, ng, cQKV, ATT, B * nwin, v.S, v.heads, v.dh, stream));
-  const void* cATT[3] = {ATT[0], ATT[1], ATT[2]};
-  // D = 384: launches of >= 128 workgroups of 128 tokens; D = 192 (LViT level 2): always -- k_mlp3<12, 3> is spill-free and 192-token workgroups
-  // make the grouped decoder launch exactly two rounds (154-162 us against k_mlp2's 181-204, tools/bench_mlp3.py)
-  const bool stream_mlp = v.stream_mlp && (v.D == 192 ? cfen_tune_stream_mlp192() != 0
-                                                      : (cfen_tune_stream_mlp() >= 2 || (cfen_tune_stream_mlp() == 1 && (long long)ng * M >= 128LL * 128)));
-  if (stream_mlp) {
-    // LViT level 3: out_proj + residual + LN2 + FFN + mlp_head + fold in one launch on fragment-stream weights (k_stream.hip)
-    Mlp3Args m[3];
-    for (int g = 0; g < ng; ++g) {
-      const std::string& n = nm[g];
-      m[g] = Mlp3Args{};
-      m[g].X = X1[g]; m[g].A = ATT[g]; m[g].Wp = P(n + ".proj.ws"); m[g].Y = nullptr; m[g].fmap = OUT[g];
-      m[g].ln_g = Pf(n + ".ln2.g"); m[g].ln_b = Pf(n + ".ln2.b");
-      m[g].Wa = P(n + ".ffn.ws"); m[g].b1a = Pf(n + ".ffn1.b"); m[g].b2a = Pf(n + ".ffn2.b");
-      m[g].Wb = P(n + ".head.ws"); m[g].b1b = Pf(n + ".head1.b"); m[g].b2b = Pf(n + ".head2.b");
-      m[g].M = M; m[g].D = v.D; m[g].H = v.hidden; m[g].eps = 1e-5f;
-      m[g].mapH = v.mapH; m[g].mapW = v.mapH; m[g].C = v.C; m[g].cs = bo.cs; m[g].ws = v.ws; m[g].p = v.p;
-    }
-    step("proj_mlp_stream");
-    block_bytes(3, DD + 4 * DH);   // X1 + attention output in, map out; W_p + the four MLP matrices
-    TRYP(K_MLP, 8 * Md * D * Hd + 2 * Md * D * D, cfen_mlp3_impl_g(dt, ng, m, stream));
-    return CFEN_OK;
-  }
-  if (!v.fused_mlp) {
-    step("proj");
-    gemm_bytes(v.D, v.Da);
-    TRYP(K_GEMM, 2 * Md * D * D, gemm(cATT, ".proj.w", nullptr, X1, nullptr, X1, v.D, v.Da, 0, nullptr));
-  }
-  if (v.fused_mlp) {
-    // LN2 + FFN + residual + mlp_head + residual + fold, hidden activations never leave registers (k_mlp.hip)
-    MlpArgs m[3];
-    for (int g = 0; g < ng; ++g) {
-      const std::string& n = nm[g];
-      m[g] = MlpArgs{};
-      m[g].X = X1[g]; m[g].Y = nullptr; m[g].fmap = v.global ? SM[g] : OUT[g];
-      m[g].A = ATT[g]; m[g].Wp = P(n + ".proj.w");   // out_proj + residual ride on the kernel's token load
-      m[g].ln_g = Pf(n + ".ln2.g"); m[g].ln_b = Pf(n + ".ln2.b");
-      m[g].W1a = P(n + ".ffn1.wk"); m[g].b1a = Pf(n + ".ffn1.b"); m[g].W2a = P(n + ".ffn2.wk"); m[g].b2a = Pf(n + ".ffn2.b");
-      m[g].W1b = P(n + ".head1.wk"); m[g].b1b = Pf(n + ".head1.b"); m[g].W2b = P(n + ".head2.wk"); m[g].b2b = Pf(n + ".head2.b");
-      m[g].M = M; m[g].D = v.D; m[g].H = v.hidden; m[g].eps = 1e-5f;
-      m[g].mapH = v.mapH; m[g].mapW = v.mapH; m[g].C = v.C; m[g].cs = v.global ? v.C : bo.cs; m[g].ws = v.ws; m[g].p = v.p;
-    }
-    step("proj_mlp_fused");
-    block_bytes(3, DD + 4 * DH);
-    TRYP(K_MLP, 8 * Md * D * Hd + 2 * Md * D * D, cfen_mlp_impl_g(dt, ng, m, stream));
-  } else {
-    // src = src + linear2(relu(linear1(LN2(src))))                             (v3:1387-1389)
-    const void* const* cHID = cHIDp;
-    if (v.ln_fold2 && cfen_tune_ln_fold()) {
-      step("ln2_ffn1");
-      gemm_bytes(v.hidden, v.D);
-      TRYP(K_GEMM, 2 * Md * D * Hd, gemm_ln(cX1, ".ffn1", HID, v.hidden, v.D, 1));
-    } else {
-      step("ln2");
-      for (int g = 0; g < ng; ++g) { lg[g] = Pf(nm[g] + ".ln2.g"); lb[g] = Pf(nm[g] + ".ln2.b"); }
-      TRYP(K_LNORM, 0, cfen_layernorm_impl_g(dt, ng, cX1, YN, lg, lb, M, v.D, 1e-5f, stream, v.Dn));
-      step("ffn1");
-      TRYP(K_GEMM, 2 * Md * D * Hd, gemm(cYN, ".ffn1.w", ".ffn1.b", nullptr, nullptr, HID, v.hidden, v.D, 1, nullptr));
-    }
-    step("ffn2");
-    gemm_bytes(v.D, v.hidden);
-    TRYP(K_GEMM, 2 * Md * D * Hd, gemm(cHID, ".ffn2.w", ".ffn2.b", X1, nullptr, X1, v.D, v.hidden, 0, nullptr));
-    // x = mlp_head(x) + x                                                      (v3:1173)
-    step("head1");
-    gemm_bytes(v.hidden, v.D);
-    TRYP(K_GEMM, 2 * Md * D * Hd, gemm(cX1, ".head1.w", ".head1.b", nullptr, nullptr, HID, v.hidden, v.D, 1, nullptr));
-    const void* dst[3];
-    for (int g = 0; g < ng; ++g) dst[g] = v.global ? SM[g] : OUT[g];
-    if (cfen_tune_fold_in_gemm()) {
-      // x = mlp_head(x) + x, folded: the GEMM's epilogue writes feature (i, j, c) of token m to its pixel of the map   (v3:1173, 1186)
-      step("head2_fold");
-      gemm_bytes(v.D, v.hidden);
-      CfenGemmPtrs gp[3];
-      for (int g = 0; g < ng; ++g)
-        gp[g] = CfenGemmPtrs{HID[g], P(nm[g] + ".head2.w"), Pf(nm[g] + ".head2.b"), X1[g], nullptr, X0[g], nullptr, nullptr, v.global && wtile,
-                             const_cast<void*>(dst[g])};
-      const CfenTokGather yg{nullptr, B, v.mapH, v.mapH, v.C, v.global ? v.C : bo.cs, v.ws, v.p};
-      TRYP(K_GEMM, 2 * Md * D * Hd, cfen_gemm_impl_g(dt, ng, gp, v.hidden, v.hidden, v.D, v.S, v.D, M, v.D, v.hidden, 0, nullptr, stream,
-                                                    v.global ? SK : nullptr, v.global ? SPLITK_BYTES : 0, &yg));
-    } else {
-      step("head2");
-      TRYP(K_GEMM, 2 * Md * D * Hd, gemm(cHID, ".head2.w", ".head2.b", X1, nullptr, X0, v.D, v.hidden, 0, nullptr));
-      step("fold");
-      TRYP(K_TOKEN, 0, cfen_patchify_impl_g(dt, ng, dst, X0, B, v.mapH, v.mapH, v.C, v.global ? v.C : bo.cs, v.ws, v.p, 1, 1, stream));
-    }
-  }
-  if (v.global && gv_skip_up) return CFEN_OK;
-  step("upsample4");
-  if (v.global) TRYP(K_TOKEN, 0, cfen_upsample4_impl_g(dt, ng, cSM, OUT, B, v.mapH, v.mapH, v.C, v.C, bo.cs, stream));
+  if (!r.upsample) return CFEN_OK;
+  c.step("upsample4");
+  TRYP(K_TOKEN, 0, cfen_upsample4_impl_g(c.dt, ng, c.DST, c.OUT, c.B, v.mapH, v.mapH, v.C, v.C, c.bo.cs, stream));
   return CFEN_OK;
 }
 
@@ -937,28 +962,21 @@ int cfen_net::run_level_g(int ng, const char* tags, int l, const std::string* in
   // globalvit_encoder_02 has its own hidden size (v3:200), so blocks of one level share launches only within the decoders
   // x4 bilinear of the GViT result inside the fuse conv (k_conv UP): the block leaves its low-resolution map in the scratch set, no k_upsample4 launch
   // and no full-resolution copy.  Not while an ActNorm of the level is still uninitialised (its raw pass reads the stored map) or stages are asked for.
-  {
-    const Vit& g0 = *gv[0].v;
-    const ConvLayer& fc = convs.at(out[0]);
-    const Buf& bo = bufs.at(out[0]);
-    const bool up = cfen_tune_up_fused() && !cfen_tune_keep_stages() && an_pending.empty() && cfg.dtype == CFEN_F16 && !g0.shrink && !lv[0].v->shrink &&
-                    fc.kind == 0 && fc.k == 1 && fc.nsrc == 2 && !fc.tile && fc.Cin == g0.C && bo.H == 4 * g0.mapH && bo.W == 4 * g0.mapH &&
-                    cfen_conv_up4_supported(cfg.dtype, ng, cfg.batch, bo.H, bo.W, fc.Cin, g0.C, fc.Cout_pad, fc.Kpad);
-    if (up) {
-      for (int g = 0; g < ng; ++g) {
-        fuse[g].up_low = at(scr_set[1 + 2 * g].small);
-        fuse[g].up_h = g0.mapH; fuse[g].up_w = g0.mapH; fuse[g].up_cs = g0.C;
-      }
-      for (int g = 0; g < ng; ++g) gvit_low.insert(gv[g].out);
-    }
-    gv_skip_up = up;
+  const Vit& g0 = *gv[0].v;
+  const ConvLayer& fc = convs.at(out[0]);
+  const Buf& bo = bufs.at(out[0]);
+  const bool up = cfen_tune_up_fused() && !cfen_tune_keep_stages() && an_pending.empty() && cfg.dtype == CFEN_F16 && !g0.shrink && !lv[0].v->shrink &&
+                fc.kind == 0 && fc.k == 1 && fc.nsrc == 2 && !fc.tile && fc.Cin == g0.C && bo.H == 4 * g0.mapH && bo.W == 4 * g0.mapH &&
+                cfen_conv_up4_supported(cfg.dtype, ng, cfg.batch, bo.H, bo.W, fc.Cin, g0.C, fc.Cout_pad, fc.Kpad);
+  for (int g = 0; g < ng && up; ++g) {
+    fuse[g].up_low = at(scr_set[1 + 2 * g].small);
+    fuse[g].up_h = g0.mapH; fuse[g].up_w = g0.mapH; fuse[g].up_cs = g0.C;
+    gvit_low.insert(gv[g].out);
   }
   hipStream_t lane_g = sg == sm ? sm : fresh_side();
   TRY(order(sm, lane_g));
   stream = lane_g;
-  int rcg = run_vit_g(ng, gv, 1);
-  gv_skip_up = false;
-  TRY(rcg);
+  TRY(run_vit_g(ng, gv, 1, up));
   stream = sm;
   if (lv[0].v->shrink) {
     // v5:1139,1190: x = conv_shrink(x) ... x = conv_extend(x); both are per-pixel, so they run on the whole map around the windowed block
@@ -1071,13 +1089,11 @@ int cfen_net::run_decoder(float* const* outs, hipStream_t sm, hipStream_t sg) {
     CfenUpConv3 u[3];
     double fl = 0.0;
     for (int g = 0; g < 3; ++g) {
-      const ConvLayer& cu = convs.at(up[g]);
-      const ConvLayer& cc = convs.at(c3[g].layer);
       const Buf& bi = bufs.at(out[g]);
       u[g] = CfenUpConv3{map_ptr(out[g]), B, bi.H, bi.W, bi.cs, P(up[g] + ".wr"), Pf(up[g] + ".scale"), Pf(up[g] + ".shift"), 1,
                          P(c3[g].layer + ".wr"), Pf(c3[g].layer + ".scale"), Pf(c3[g].layer + ".shift"), 1, map_ptr(c3[g].out),
                          cfen_tune_keep_stages() ? map_ptr(up[g]) : nullptr};
-      fl += B * (2.0 * cu.Cin_real * cu.Cout * 16.0 * bi.H * bi.W + 2.0 * cc.Cout * (double)cc.Cin_real * 9.0 * 4.0 * bi.H * bi.W);
+      fl += convs.at(up[g]).flops(B) + convs.at(c3[g].layer).flops(B);
     }
     // "net.tail_fused" = 2 (round 5): the reflect-pad 7x7 + tanh rides along too (k_tail.hip: a workgroup walks down a 64-column strip, both intermediate
     // maps in LDS) -- unless the stage maps are asked for
@@ -1096,7 +1112,7 @@ int cfen_net::run_decoder(float* const* outs, hipStream_t sm, hipStream_t sg) {
       d7[g].scale = Pf(c7[g].layer + ".scale"); d7[g].shift = Pf(c7[g].layer + ".shift");
       d7[g].act = 2; d7[g].Cout = z.Cout; d7[g].Cout_pad = z.Cout_pad;
       d7[g].out = outs[g]; d7[g].out_nchw_f32 = mode; d7[g].cs_out = z.Cout_pad;
-      fl += B * 2.0 * z.Cout * (double)z.Cin_real * 49.0 * bm.H * bm.W;
+      fl += z.flops(B);
     }
     if (whole) {
       label = up[0] + " + " + c3[0].layer + " + " + c7[0].layer + " (x3, fused)";
@@ -1115,7 +1131,7 @@ int cfen_net::run_decoder(float* const* outs, hipStream_t sm, hipStream_t sg) {
 }
 
 int cfen_net::forward(const float* x, float* xr, float* xs, float* xd) {
-  const int dt = cfg.dtype, B = cfg.batch, N = cfg.load_size;
+  const int dt = cfg.dtype, B = cfg.batch;
   const hipStream_t s0 = stream;
   const bool par = parallel && !profiling;
   if (par && !side[0]) {
@@ -1146,9 +1162,8 @@ int cfen_net::forward(const float* x, float* xr, float* xs, float* xd) {
   const bool use_head5 = head5 && cfen_tune_head5() && !cfen_tune_head_fused();
   if (use_head5) {
     // the input layout pass and head.0.0 in ONE launch: the conv stages its halo straight from the fp32 NCHW tensor / the uint8 HWC image
-    const ConvLayer& c = convs.at("head.0.0");
     label = "head.0.0 (from the network input)";
-    TRYP(K_CONV, B * 2.0 * c.Cout * (double)c.Cin_real * c.k * c.k * (double)full * full,
+    TRYP(K_CONV, convs.at("head.0.0").flops(B),
          cfen_head5_impl(dt, input_u8, x, P("head.0.0.w5"), Pf("head.0.0.scale"), Pf("head.0.0.shift"), map_ptr("head.conv5"), B, full, full,
                          bufs.at("head.conv5").cs, 0, stream));
   } else if (input_u8) {
@@ -1165,10 +1180,7 @@ int cfen_net::forward(const float* x, float* xr, float* xs, float* xd) {
     // one launch, the 5x5 output and the ResBlock's hidden map stay in LDS (k_conv_tile.hip: k_head_fused)
     label = "head (conv5 + ResBlock fused)";
     double fl = 0.0;
-    for (const char* l : {"head.0.0", "head.0.1.body.0", "head.0.1.body.2"}) {
-      const ConvLayer& c = convs.at(l);
-      fl += B * 2.0 * c.Cout * (double)c.Cin_real * c.k * c.k * (double)full * full;
-    }
+    for (const char* l : {"head.0.0", "head.0.1.body.0", "head.0.1.body.2"}) fl += convs.at(l).flops(B);
     TRYP(K_CONV, fl, cfen_head_fused_impl(dt, map_ptr("input"), map_ptr("head"), P("head.0.0.wr"), Pf("head.0.0.scale"), Pf("head.0.0.shift"),
                                           P("head.0.1.body.0.wr"), Pf("head.0.1.body.0.scale"), Pf("head.0.1.body.0.shift"), P("head.0.1.body.2.wr"),
                                           Pf("head.0.1.body.2.scale"), Pf("head.0.1.body.2.shift"), B, full, full, stream));
@@ -1180,8 +1192,7 @@ int cfen_net::forward(const float* x, float* xr, float* xs, float* xd) {
         cfen_resblock_fused_supported(dt, bufs.at("head.conv5").cs, ca.Cout, full, full)) {
       // ResBlock in one launch: the hidden map (head.res_mid) stays in LDS (k_fuse.hip)
       label = "head.0.1 (ResBlock fused)";
-      const double fl = B * 2.0 * (double)full * full * 9.0 * ((double)ca.Cout * ca.Cin_real + (double)cb.Cout * cb.Cin_real);
-      TRYP(K_CONV, fl, cfen_resblock_fused_impl(dt, map_ptr("head.conv5"), map_ptr("head"), P("head.0.1.body.0.wr"), Pf("head.0.1.body.0.scale"),
+      TRYP(K_CONV, ca.flops(B) + cb.flops(B), cfen_resblock_fused_impl(dt, map_ptr("head.conv5"), map_ptr("head"), P("head.0.1.body.0.wr"), Pf("head.0.1.body.0.scale"),
                                                Pf("head.0.1.body.0.shift"), P("head.0.1.body.2.wr"), Pf("head.0.1.body.2.scale"),
                                                Pf("head.0.1.body.2.shift"), B, full, full, stream));
     } else {
@@ -1306,19 +1317,25 @@ int cfen_net_missing_params(const cfen_net* net, char* buf, size_t buflen) {
   return count;
 }
 
+// what a forward or a capture (`who`: the prefix of the messages) needs before the first launch: a workspace of the right size and alignment, every parameter set
+static int ready(const cfen_net* net, const char* who, const void* workspace, size_t workspace_bytes) {
+  if (workspace_bytes < net->ws_bytes) {
+    cfen_set_error("%s: workspace has %zu bytes, %zu needed", who, workspace_bytes, net->ws_bytes);
+    return CFEN_ERR_STATE;
+  }
+  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  for (const auto& kv : net->params)
+    if (!kv.second.ptr) {
+      cfen_set_error("%s: parameter '%s' was never set", who, kv.first.c_str());
+      return CFEN_ERR_STATE;
+    }
+  return CFEN_OK;
+}
+
 int cfen_net_forward(cfen_net* net, const float* x, float* xr, float* xs, float* xd, void* workspace, size_t workspace_bytes,
                      void* stream) {
   CFEN_CHECK_ARG(net && x && xr && xs && xd && workspace, "net_forward: null argument");
-  if (workspace_bytes < net->ws_bytes) {
-    cfen_set_error("net_forward: workspace has %zu bytes, %zu needed", workspace_bytes, net->ws_bytes);
-    return CFEN_ERR_STATE;
-  }
-  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "net_forward: workspace must be 256-byte aligned");
-  for (const auto& kv : net->params)
-    if (!kv.second.ptr) {
-      cfen_set_error("net_forward: parameter '%s' was never set", kv.first.c_str());
-      return CFEN_ERR_STATE;
-    }
+  TRY(ready(net, "net_forward", workspace, workspace_bytes));
   net->base = (unsigned char*)workspace;
   net->stream = (hipStream_t)stream;
   TRY(net->prime_workspace(false));
@@ -1330,16 +1347,7 @@ int cfen_net_forward(cfen_net* net, const float* x, float* xr, float* xs, float*
 int cfen_net_graph_capture(cfen_net* net, const float* x, float* xr, float* xs, float* xd, void* workspace, size_t workspace_bytes,
                            int32_t* graph_id) {
   CFEN_CHECK_ARG(net && x && xr && xs && xd && workspace && graph_id, "graph_capture: null argument");
-  if (workspace_bytes < net->ws_bytes) {
-    cfen_set_error("graph_capture: workspace has %zu bytes, %zu needed", workspace_bytes, net->ws_bytes);
-    return CFEN_ERR_STATE;
-  }
-  CFEN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "graph_capture: workspace must be 256-byte aligned");
-  for (const auto& kv : net->params)
-    if (!kv.second.ptr) {
-      cfen_set_error("graph_capture: parameter '%s' was never set", kv.first.c_str());
-      return CFEN_ERR_STATE;
-    }
+  TRY(ready(net, "graph_capture", workspace, workspace_bytes));
   CfenGraphRecorder rec;
   if (hipGraphCreate(&rec.graph, 0) != hipSuccess) {
     cfen_set_error("graph_capture: hipGraphCreate failed");
@@ -1455,21 +1463,12 @@ int cfen_net_chain_error_words(const cfen_net* net, const void** words, int n) {
 
 double cfen_net_flops_per_image(const cfen_net* net) {
   if (!net) return 0.0;
-  const int B = net->cfg.batch;
   double f = 0.0;
   for (const Vit& v : net->vits) {   // 2T(5D^2 + 4DH) + 4 T S D
     const double T = (double)(v.mapH / v.ws) * (v.mapH / v.ws) * v.S;
     f += 2.0 * T * (5.0 * v.Dn * v.Dn + 4.0 * (double)v.Dn * v.hidden) + 4.0 * T * v.S * v.Dn;
   }
-  for (const auto& kv : net->convs) {
-    const ConvLayer& c = kv.second;
-    const double e = (double)c.out_edge;
-    if (c.kind == 1)
-      f += 2.0 * c.Cin_real * c.Cout * 16.0 * (e / 2.0) * (e / 2.0);   // 2*Cin*Cout*16*Hin*Win
-    else
-      f += 2.0 * c.Cout * (double)c.Cin_real * c.nsrc * c.k * c.k * e * e;
-  }
-  (void)B;
+  for (const auto& kv : net->convs) f += kv.second.flops(1);
   return f;
 }
 
