@@ -199,6 +199,11 @@ HEADERS = {
         "cfen_flicker_bytes": (c_size_t, [_I, _I, _I]),
         "cfen_flicker_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     },
+    # per-plane scores against a ground-truth stream
+    "cfen_planes.h": {
+        "cfen_plane_metrics_bytes": (c_size_t, [_I, _I, _I, _I]),
+        "cfen_plane_metrics": (_I, [_P, c_size_t, _P, c_size_t, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    },
 }
 SIGNATURES = HEADERS["cfen_hip.h"]          # the core table, by the name the frozen ABI's tests and documents use
 

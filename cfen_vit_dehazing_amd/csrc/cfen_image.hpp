@@ -1,6 +1,6 @@
-// What the image-side kernels share (k_guided, k_temporal, k_metrics, k_colordiff, k_noref, k_png): window and source coordinates, the
-// rounding to a byte, the full-resolution apply kernel of k_guided / k_temporal with its launch, and the fixed-order fp64 reductions the
-// scores are built from.  Each argument below is made here once; the .hip files state only what is their own.
+// What the image-side kernels share (k_guided, k_temporal, k_metrics, k_planes, k_colordiff, k_noref, k_png): window and source coordinates,
+// the rounding to a byte, the full-resolution apply kernel of k_guided / k_temporal with its launch, the fixed-order fp64 reductions the
+// scores are built from, and the SSIM tile (window, row and column pass) of k_metrics / k_planes.  Each argument below is made here once; the .hip files state only what is their own.
 #pragma once
 #include <math.h>
 
@@ -187,5 +187,62 @@ CFEN_DEV void img_reduce_partials(const double* __restrict__ p, int n, double (*
       for (int k = 0; k < NP; ++k) red[k][tid] += red[k][tid + m];
     }
     __syncthreads();
+  }
+}
+
+// ---- the SSIM tile (k_metrics, k_planes) --------------------------------------------------------------------------------------------------
+// A workgroup of 256 threads owns MT_H x MT_W = 24 x 64 window positions: it stages the (24 + 10) x (64 + 10) values under them of both images
+// as fp32 on the [0,1] scale (zeros past the edge) into sa / sb, then
+//   row pass   : the 11-tap filter along x over a, b, a^2, b^2, ab -> five (34 x 64) planes in hq; a wave reads 64 consecutive floats per tap;
+//   column pass: a thread owns one column and MT_R = 6 consecutive rows, reads the 16 row-filtered values under them once per plane and
+//                leaves the five filtered quantities of its 6 window positions in f.
+// The order of every fmaf is written out here, so every kernel built on the tile forms the same bits from the same staged values.
+constexpr int MT_H = 24, MT_W = 64, MT_HALO = 10, MT_TAPS = 11;
+constexpr int MT_SH = MT_H + MT_HALO, MT_SW = MT_W + MT_HALO;   // staged rows / columns
+constexpr int MT_R = MT_H / 4;                                   // rows per thread in the column pass (4 waves, one column per lane)
+
+// exp(-(i - 5)^2 / (2 * 1.5^2)) / sum, evaluated in fp64 and rounded once
+[[maybe_unused]] static __constant__ const float MT_G[MT_TAPS] = {1.028380084e-03f, 7.598758135e-03f, 3.600077213e-02f, 1.093606895e-01f,
+                                                                  2.130055377e-01f, 2.660117249e-01f, 2.130055377e-01f, 1.093606895e-01f,
+                                                                  3.600077213e-02f, 7.598758135e-03f, 1.028380084e-03f};
+
+// tiles along an edge of L values: the window positions L - 10 in steps of T (the last tile also owns the edge's 10 values without a window)
+static inline long long metrics_tiles(int L, int T) { return ((long long)L - MT_HALO + T - 1) / T; }
+
+// row pass: column `lane` of rows wave, wave + 4, ...  The caller puts a barrier between the two passes.
+CFEN_DEV void ssim_row_pass(const float (*sa)[MT_SW], const float (*sb)[MT_SW], float (*hq)[MT_SH][MT_W], int wave, int lane) {
+  for (int r = wave; r < MT_SH; r += 4) {
+    float s1 = 0.f, s2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
+#pragma unroll
+    for (int j = 0; j < MT_TAPS; ++j) {
+      const float w = MT_G[j], a = sa[r][lane + j], v = sb[r][lane + j];
+      s1 = fmaf(w, a, s1);
+      s2 = fmaf(w, v, s2);
+      s11 = fmaf(w, a * a, s11);
+      s22 = fmaf(w, v * v, s22);
+      s12 = fmaf(w, a * v, s12);
+    }
+    hq[0][r][lane] = s1;
+    hq[1][r][lane] = s2;
+    hq[2][r][lane] = s11;
+    hq[3][r][lane] = s22;
+    hq[4][r][lane] = s12;
+  }
+}
+
+// column pass: column `lane`, rows wave * MT_R .. + MT_R - 1
+CFEN_DEV void ssim_col_pass(const float (*hq)[MT_SH][MT_W], int wave, int lane, float (&f)[5][MT_R]) {
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    float col[MT_R + MT_HALO];
+#pragma unroll
+    for (int i = 0; i < MT_R + MT_HALO; ++i) col[i] = hq[q][wave * MT_R + i][lane];
+#pragma unroll
+    for (int k = 0; k < MT_R; ++k) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < MT_TAPS; ++j) s = fmaf(MT_G[j], col[k + j], s);
+      f[q][k] = s;
+    }
   }
 }

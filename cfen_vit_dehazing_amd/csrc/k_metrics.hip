@@ -9,9 +9,9 @@
 //                       1. stages the (24 + 10) x (64 + 10) pixels under those windows of both images in LDS as fp32 (zeros past the image), and adds
 //                          the squared error of the pixels the tile OWNS: [y0, y0 + 24) x [x0, x0 + 64), the last tile row / column up to the image
 //                          edge -- so the 10-pixel border without a window of its own is counted, every pixel exactly once;
-//                       2. row pass: the 11-tap filter along x over a, b, a^2, b^2, ab -> five (34 x 64) planes in LDS; a wave reads 64 consecutive
+//                       2. row pass (ssim_row_pass of cfen_image.hpp, shared with k_planes.hip): the 11-tap filter along x over a, b, a^2, b^2, ab -> five (34 x 64) planes in LDS; a wave reads 64 consecutive
 //                          floats per tap (conflict-free);
-//                       3. column pass: a thread owns one column and 6 consecutive rows, reads the 16 row-filtered values under them once per plane
+//                       3. column pass (ssim_col_pass): a thread owns one column and 6 consecutive rows, reads the 16 row-filtered values under them once per plane
 //                          and forms 6 SSIM map values.
 //                     Per-thread sums are fp64 (the squared error of uint8 input is summed in integers first: exact), reduced over the wave with
 //                     shuffles, over the 4 waves through LDS in wave order, and written as this tile's (sse, ssim sum) pair to `part`.
@@ -30,14 +30,6 @@
 #include "cfen_image.hpp"
 
 namespace {
-
-constexpr int MT_H = 24, MT_W = 64, MT_HALO = 10, MT_TAPS = 11;
-constexpr int MT_SH = MT_H + MT_HALO, MT_SW = MT_W + MT_HALO;   // staged rows / columns
-constexpr int MT_R = MT_H / 4;                                   // rows per thread in the column pass (4 waves, one column per lane)
-
-// exp(-(i - 5)^2 / (2 * 1.5^2)) / sum, evaluated in fp64 and rounded once
-__constant__ const float MT_G[MT_TAPS] = {1.028380084e-03f, 7.598758135e-03f, 3.600077213e-02f, 1.093606895e-01f, 2.130055377e-01f, 2.660117249e-01f,
-                                          2.130055377e-01f, 1.093606895e-01f, 3.600077213e-02f, 7.598758135e-03f, 1.028380084e-03f};
 
 struct MetricsGeom {
   int C, H, W, nty, ntx;
@@ -139,40 +131,11 @@ CFEN_DEV void metrics_tile(const void* __restrict__ pa, const void* __restrict__
         pool.b[o] = (((sb[2 * r][2 * q] + sb[2 * r][2 * q + 1]) + sb[2 * r + 1][2 * q]) + sb[2 * r + 1][2 * q + 1]) * 0.25f;
       }
     }
-    // 2. row pass: column `lane` of rows wave, wave + 4, ...
-    for (int r = wave; r < MT_SH; r += 4) {
-      float s1 = 0.f, s2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
-#pragma unroll
-      for (int j = 0; j < MT_TAPS; ++j) {
-        const float w = MT_G[j], a = sa[r][lane + j], v = sb[r][lane + j];
-        s1 = fmaf(w, a, s1);
-        s2 = fmaf(w, v, s2);
-        s11 = fmaf(w, a * a, s11);
-        s22 = fmaf(w, v * v, s22);
-        s12 = fmaf(w, a * v, s12);
-      }
-      hq[0][r][lane] = s1;
-      hq[1][r][lane] = s2;
-      hq[2][r][lane] = s11;
-      hq[3][r][lane] = s22;
-      hq[4][r][lane] = s12;
-    }
+    // 2. row pass, 3. column pass (cfen_image.hpp)
+    ssim_row_pass(sa, sb, hq, wave, lane);
     __syncthreads();
-    // 3. column pass: column `lane`, rows wave * MT_R .. + MT_R - 1
     float f[5][MT_R];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      float col[MT_R + MT_HALO];
-#pragma unroll
-      for (int i = 0; i < MT_R + MT_HALO; ++i) col[i] = hq[q][wave * MT_R + i][lane];
-#pragma unroll
-      for (int k = 0; k < MT_R; ++k) {
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < MT_TAPS; ++j) s = fmaf(MT_G[j], col[k + j], s);
-        f[q][k] = s;
-      }
-    }
+    ssim_col_pass(hq, wave, lane, f);
     if (x0 + lane + MT_HALO < W) {
 #pragma unroll
       for (int k = 0; k < MT_R; ++k)
@@ -222,8 +185,6 @@ __global__ __launch_bounds__(256) void k_image_metrics_finish(const double* __re
     out[2 * b + 1] = red[1][0] / count;
   }
 }
-
-inline long long metrics_tiles(int L, int T) { return ((long long)L - MT_HALO + T - 1) / T; }
 
 constexpr int MS_LEVELS = 5, MS_MIN_EDGE = MT_TAPS << (MS_LEVELS - 1);      // level 4 must still hold one window: 176
 

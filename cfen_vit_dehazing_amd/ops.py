@@ -752,6 +752,35 @@ def flicker_u8(guide, prev_guide, tgt, prev_tgt, vec, block, tol, out=None):
     return out
 
 
+def plane_metrics(a, b, H, W, chroma, depth=8, prev=None):
+    """cfen_plane_metrics (include/cfen_planes.h): B frames of a YCbCr stream against B frames of a ground-truth stream, plane by plane on the
+    samples as stored.  a, b: (B, frame_bytes) uint8 CUDA tensors, the FRAME payloads of a .y4m stream as they are (rows any number >=
+    frame_bytes of bytes apart; at depth 9 .. 16 little-endian 16-bit samples at even addresses); chroma: one of yuv.CHROMA; prev: None, or
+    (a_prev, b_prev), the frame pair before frame 0 as two (frame_bytes,) tensors.  Returns (sse, dt, ssim, count), each (B, 3) over the planes
+    Y, Cb, Cr: sse, dt and count int64, ssim float64 (NaN for a plane under 11 samples on a side or absent).  Two launches; the same bits at
+    every batch size, stride, alignment and stream."""
+    from . import yuv
+    code = yuv.chroma_code(chroma)
+    depth = _int_arg("plane_metrics", "depth", depth, 8, yuv.MAX_DEPTH)
+    H, W = _int_arg("plane_metrics", "H", H, 1, yuv.MAX_EDGE), _int_arg("plane_metrics", "W", W, 1, yuv.MAX_EDGE)
+    nbytes = yuv.frame_bytes(H, W, chroma, depth)
+    sa, sb = _yuv_frames("plane_metrics (a)", a, nbytes), _yuv_frames("plane_metrics (b)", b, nbytes)
+    if a.shape[0] != b.shape[0] or a.device != b.device:
+        raise ValueError("plane_metrics: a holds %d frames on %s and b %d on %s" % (a.shape[0], a.device, b.shape[0], b.device))
+    B, dev = a.shape[0], a.device
+    pa = pb = None
+    if prev is not None:
+        pa, pb = prev
+        for name, t in (("prev[0]", pa), ("prev[1]", pb)):
+            _tensor_arg("plane_metrics", name, t, (nbytes,), torch.uint8, like=a)
+    lib = _lib.load()
+    scratch = _scratch_for("plane_metrics", lib.cfen_plane_metrics_bytes, (B, H, W, code), dev, "B <= %d, H W <= 2^31" % yuv.MAX_BATCH)
+    out = torch.empty(B, 3, 4, dtype=torch.int64, device=dev)
+    check(lib.cfen_plane_metrics(ptr(a), sa, ptr(b), sb, ptr(pa), ptr(pb), B, H, W, code, depth, ptr(scratch), ptr(out), current_stream()),
+          "plane_metrics")
+    return out[:, :, 0], out[:, :, 1], out.view(torch.float64)[:, :, 2], out[:, :, 3]          # views of one tensor: no launch of their own
+
+
 def image_metrics(a, b, value_range=(-1.0, 1.0), out=None):
     """cfen_image_metrics: per image pair (sse, ssim) as two float64 CUDA tensors of shape (B,), in one fused pass.
 

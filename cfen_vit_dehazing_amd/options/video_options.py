@@ -5,6 +5,7 @@
   * --u8_input is always on: the converted frames are bytes.
   * --in_flight stays 1: the loop has its own reader and writer threads (--video_buffers).
   * --video_depth auto lets a stream of 9 to 16 bits per sample in (the float route of video.run); the default, 8, refuses it as always.
+  * --eval_gt CLEAR.y4m scores the stream that leaves against a ground-truth stream of the same geometry.
   * the options are recorded in <checkpoints_dir>/<name>/video_opt.txt; opt.txt, which test.py writes, is left as it was."""
 import os
 
@@ -67,6 +68,12 @@ class VideoOptions(TestOptions):
         p.add_argument('--flicker_down', type=str, default=None,
                        help='--eval_flicker: integer factor >= 1 between the frame and the working resolution, or auto = ceil(max(H, W) / 1024) (default auto)')
         p.add_argument('--flicker_csv', type=str, default=None, help='--eval_flicker: where flicker.csv goes (default: beside --out; required when --out is -)')
+        p.add_argument('--eval_gt', type=str, default=None, metavar='CLEAR.y4m',
+                       help='(extension) score the stream that leaves against this ground-truth .y4m file (DESIGN section 24): per frame PSNR '
+                            'and SSIM of the Y, Cb and Cr planes on the samples as stored, and a temporal error; writes gt.csv and prints one '
+                            'summary line. The file must have the size, the C tag and the interlacing of --in and at least as many frames; - is '
+                            'refused. Works on every route, 8-bit and deep. The stream itself is unchanged')
+        p.add_argument('--gt_csv', type=str, default=None, help='--eval_gt: where gt.csv goes (default: beside --out; required when --out is -)')
         for a in p._actions:
             if a.dest == 'dataroot':
                 a.required = False
@@ -137,6 +144,33 @@ class VideoOptions(TestOptions):
             raise ValueError(str(e).replace('--flicker: ', '--flicker_', 1))
         return [a for k in self.FLICKER if k not in given for a in ('--flicker_' + k, str(flicker.DEFAULTS[k]))]
 
+    @staticmethod
+    def _without_gt(text):
+        """a run without --eval_gt prints and records what it always did"""
+        return ''.join(l for l in text.splitlines(True) if not l.startswith(('eval_gt', 'gt_csv')))
+
+    @staticmethod
+    def _check_gt(first):
+        """the refusals of --eval_gt and --gt_csv; with an input FILE the two headers are compared here, so that a ground truth of another
+        geometry is refused at parsing (a pipe: video.run compares as soon as it has read the input's header)"""
+        if not first.eval_gt:
+            if first.gt_csv:
+                raise ValueError('--gt_csv is where --eval_gt writes: it needs --eval_gt')
+            return
+        if first.eval_gt == '-':
+            raise ValueError('--eval_gt takes a .y4m file: - (stdin) is refused, it is where --in - reads the hazy stream')
+        if first.video_out == '-' and not first.gt_csv:
+            raise ValueError('--eval_gt with --out -: say where gt.csv goes with --gt_csv PATH')
+        from .. import video
+        max_depth = 16 if first.video_depth == 'auto' else 8
+        gt = video.peek_header(first.eval_gt, max_depth)          # OSError (a ValueError to the caller below) or Y4MError: the run ends here
+        if first.video_in != '-':
+            try:
+                src = video.peek_header(first.video_in, max_depth)
+            except (OSError, video.Y4MError):
+                return                                            # video.run says what is wrong with the input
+            video.check_gt_header(src, gt, first.eval_gt)
+
     def _check_temporal(self, first):
         """the refusals of the --temporal options; returns the defaults of those not given, as arguments"""
         from .. import temporal
@@ -179,6 +213,10 @@ class VideoOptions(TestOptions):
             tag = video.peek_deep_tag(first.video_in)
             if tag is not None:
                 video.refuse_deep_flags(first, tag)
+        try:
+            self._check_gt(first)
+        except OSError as e:
+            raise ValueError('--eval_gt %s: %s' % (first.eval_gt, e.strerror or e))
         depth_given = first.video_depth != '8'
         extra_temporal = self._check_temporal(first) + self._check_temporal_mc(first) + self._check_flicker(first)
         mc_on = bool(first.temporal and first.temporal_mc)
@@ -203,6 +241,7 @@ class VideoOptions(TestOptions):
         text = text if mc_on else self._without_temporal_mc(text)
         text = text if first.eval_flicker else self._without_flicker(text)
         text = text if depth_given else self._without_video_depth(text)
+        text = text if first.eval_gt else self._without_gt(text)
         sys.stdout.write(text)
         sys.stdout.flush()
         if opt.dist_rank == 0:
@@ -212,6 +251,7 @@ class VideoOptions(TestOptions):
                 recorded = recorded if mc_on else self._without_temporal_mc(recorded)
                 recorded = recorded if first.eval_flicker else self._without_flicker(recorded)
                 recorded = recorded if depth_given else self._without_video_depth(recorded)
+                recorded = recorded if first.eval_gt else self._without_gt(recorded)
                 if before is None:
                     os.remove(opt_txt)
                 else:
@@ -225,4 +265,6 @@ class VideoOptions(TestOptions):
             opt.noref_csv = os.path.join(os.path.dirname(os.path.abspath(opt.video_out)), 'noref.csv')
         if opt.eval_flicker and not opt.flicker_csv:
             opt.flicker_csv = os.path.join(os.path.dirname(os.path.abspath(opt.video_out)), 'flicker.csv')
+        if opt.eval_gt and not opt.gt_csv:
+            opt.gt_csv = os.path.join(os.path.dirname(os.path.abspath(opt.video_out)), 'gt.csv')
         return opt

@@ -7,7 +7,10 @@ sample (--video_depth auto) takes the same loop on floats: ops.yuv16_to_rgb_f32 
 
 Threads: one reader fills pinned host buffers, one writer drains them; the main thread issues, per batch and on ONE stream, the copy in, the
 conversion, the forward, the conversion back and the copy out.  The ring holds --video_buffers slots; a slot goes reader -> main -> writer ->
-reader.  Everything on the device happens in frame order on that stream, so the output does not depend on timing or on the number of slots."""
+reader.  Everything on the device happens in frame order on that stream, so the output does not depend on timing or on the number of slots.
+
+--eval_gt CLEAR.y4m scores the payload that leaves against a ground-truth stream, plane by plane (ops.plane_metrics, include/cfen_planes.h;
+gtscore.py): the main thread reads the ground-truth frames of a batch into the slot's third pinned buffer after the copy out is issued."""
 import os
 import queue
 import sys
@@ -319,6 +322,31 @@ def peek_deep_tag(path):
     return info["ctag"] if info["depth"] > 8 else None
 
 
+def peek_header(path, max_depth=8):
+    """parse_header of the first line of the y4m file at `path`; OSError if it cannot be read, Y4MError if it is not a stream this project reads"""
+    with open(path, "rb") as f:
+        return parse_header(f.readline(MAX_HEADER), max_depth)
+
+
+def _interlacing(info):
+    return next((t[1:] for t in info["tags"] if t[0] == "I"), "?")
+
+
+def check_gt_header(src, gt, gt_name="the ground truth"):
+    """--eval_gt: the ground truth's header against the input's (two parse_header dicts): the planes are compared sample by sample, so the size,
+    the C tag (and with it the depth) and the interlacing must be equal.  Y4MError naming both values"""
+    def ctag(info):
+        return info["ctag"] or "C420jpeg (no C tag)"
+    same_format = (src["chroma"], src["depth"]) == (gt["chroma"], gt["depth"])          # C420 and no C tag at all are C420jpeg too
+    for what, a, b, equal in (("width", src["width"], gt["width"], src["width"] == gt["width"]),
+                              ("height", src["height"], gt["height"], src["height"] == gt["height"]),
+                              ("C tag", ctag(src), ctag(gt), same_format),
+                              ("interlacing", "I" + _interlacing(src), "I" + _interlacing(gt), _interlacing(src) == _interlacing(gt))):
+        if not equal:
+            raise Y4MError("--eval_gt %s: its %s is %s but the input's is %s: a ground truth is compared sample by sample and needs the input's "
+                           "size, C tag and interlacing" % (gt_name, what, b, a))
+
+
 class UnsafeHalfFrames(Y4MError):
     """--precision half: a guard check failed after fp16 frames had already left in the stream"""
 
@@ -336,6 +364,11 @@ def run(opt, log=print):
     deep = depth > 8
     if deep:
         refuse_deep_flags(opt, reader.ctag)   # a pipe: as soon as the header is read, before the checkpoint is loaded and before any output
+    gt_reader = None
+    if getattr(opt, "eval_gt", None):
+        # as the deep refusal above: for a piped input this is the first moment the two headers can be compared
+        gt_reader = Y4MReader(opt.eval_gt, max_depth=16 if deep_allowed else 8)
+        check_gt_header(parse_header(reader.header, 16 if deep_allowed else 8), parse_header(gt_reader.header, 16 if deep_allowed else 8), opt.eval_gt)
     matrix = pick_matrix(opt.video_matrix, H)
     full = pick_range(opt.video_range, reader.color_range) == "full"
     log("video: %d x %d C%s%s, matrix %s (%s), range %s (%s)" % (W, H, chroma, ", %d bits per sample (%s)" % (depth, "float route" if deep else "uint8 route")
@@ -350,6 +383,10 @@ def run(opt, log=print):
         raise Y4MError("the frames are %d x %d but the generator takes %d x %d: give %s--tile (overlapping tiles)"
                        % (W, H, T, T, "" if deep else "--fit (one resampled forward per frame) or "))
     n_known = reader.check_whole_file()       # a file cut short is refused here, before any forward
+    if gt_reader is not None:
+        gt_known = gt_reader.check_whole_file()
+        if n_known is not None and gt_known is not None and gt_known < n_known:
+            raise Y4MError("--eval_gt %s holds %d frames but the input holds %d: frame %d has no ground truth" % (opt.eval_gt, gt_known, n_known, gt_known))
     model = create_model(opt)
     model.setup(opt)
     model.set_noref_scoring(False)            # the frames are scored here (all three routes), not in model.test()
@@ -367,6 +404,8 @@ def run(opt, log=print):
     slots = []
     for _ in range(opt.video_buffers):
         pins = (torch.empty(B, nb, dtype=torch.uint8).pin_memory(), torch.empty(B, nb, dtype=torch.uint8).pin_memory())
+        if gt_reader is not None:
+            pins += (torch.empty(B, nb, dtype=torch.uint8).pin_memory(),)          # the ground truth of the slot's frames
         slots.append(Slot(pins[0].numpy(), pins[1].numpy(), extra=pins))
     d_in = torch.empty(B, nb, dtype=torch.uint8, device=dev)
     d_out = torch.empty(B, nb, dtype=torch.uint8, device=dev)
@@ -396,6 +435,28 @@ def run(opt, log=print):
         log("video: flicker along the motion at %d x %d (1/%d), search within +-%d pixels, blocks of %d x %d, bias %d / 16, tolerance %d levels"
             % (w, h, S, scorer.range, scorer.block, scorer.block, scorer.bias, scorer.tol))
 
+    gt_scorer, gt_rows, d_gt = None, [], None
+    if gt_reader is not None:
+        from . import gtscore
+        gt_scorer = gtscore.Scorer(H, W, chroma, depth)
+        d_gt = torch.empty(B, nb, dtype=torch.uint8, device=dev)
+        seconds["gt"] = 0.0
+        log("video: scoring against %s, per plane on the %d-bit samples that leave" % (opt.eval_gt, depth))
+
+    def score_gt(s):
+        """--eval_gt: the slot's ground-truth frames go through the slot's pinned buffer to the device and are compared with the payload in d_out,
+        the very bytes that leave.  The call waits for its own results, so the pinned buffer is free again when the slot comes back."""
+        t1 = time.perf_counter()
+        pin_gt = s.extra[2]
+        rows_gt = pin_gt.numpy()
+        for k in range(s.n):
+            if not gt_reader.read_frame_into(rows_gt[k]):
+                raise Y4MError("--eval_gt %s ends before frame %d of the input: every frame needs its ground truth" % (opt.eval_gt, s.first + k))
+        d_gt[:s.n].copy_(pin_gt[:s.n], non_blocking=True)
+        for k, row in enumerate(gt_scorer.step(d_out[:s.n], d_gt[:s.n])):
+            gt_rows.append(("frame_%06d" % (s.first + k), row))
+        seconds["gt"] += time.perf_counter() - t1
+
     def through_model(x, first):
         """the model's own batch route, the one test.py takes (the half guard included where test.py applies it)"""
         model.set_input({"B": x, "B_paths": ["frame_%06d" % (first + k) for k in range(x.shape[0])]})
@@ -406,7 +467,7 @@ def run(opt, log=print):
         """the float route of a stream of 9 .. 16 bits per sample: the samples become (n,3,H,W) float32 in [-1, 1] (include/cfen_yuv16.h), the
         generator's float outputs are rounded to samples of the same depth; nothing on the way is a byte"""
         n = s.n
-        pin_in, pin_out = s.extra
+        pin_in, pin_out = s.extra[:2]
         d_in[:n].copy_(pin_in[:n], non_blocking=True)
         x = ops.yuv16_to_rgb_f32(d_in[:n], H, W, chroma, depth, matrix, full, out=rgb[:n])
 
@@ -434,11 +495,13 @@ def run(opt, log=print):
         pin_out[:n].copy_(d_out[:n], non_blocking=True)
         done = torch.cuda.Event()
         done.record(stream)
+        if gt_scorer is not None:
+            score_gt(s)                       # after the copy out is on its way: the writer does not wait for the scores
         return done
 
     def process(s):
         n = s.n
-        pin_in, pin_out = s.extra
+        pin_in, pin_out = s.extra[:2]
         d_in[:n].copy_(pin_in[:n], non_blocking=True)
         x = ops.yuv_to_rgb_u8(d_in[:n], H, W, chroma, matrix, full, out=rgb[:n])
         if route != "tile":
@@ -478,6 +541,8 @@ def run(opt, log=print):
         pin_out[:n].copy_(d_out[:n], non_blocking=True)
         done = torch.cuda.Event()
         done.record(stream)
+        if gt_scorer is not None:
+            score_gt(s)                       # after the copy out is on its way: the writer does not wait for the scores
         return done
 
     t_start = time.perf_counter()
@@ -497,6 +562,15 @@ def run(opt, log=print):
             f.write(flicker.format_csv(flicker_rows))
         log(flicker.summary_line([r for _, r in flicker_rows]))
         log("flicker: wrote %s" % opt.flicker_csv)
+    if gt_scorer is not None:
+        with open(opt.gt_csv, "w") as f:
+            f.write(gtscore.format_csv(gt_rows))
+        log(gtscore.summary_line([r for _, r in gt_rows]))
+        log("gt: wrote %s" % opt.gt_csv)
+        extra = gt_reader.read_frame_into(bytearray(nb))
+        gt_reader.close()
+        if extra:
+            raise Y4MError("--eval_gt %s holds more frames than the %d of the input: the two streams do not belong together" % (opt.eval_gt, frames))
     log("video: route %s, %d frames per batch, %d buffers; main-thread seconds %s" % (route, B, opt.video_buffers, {k: round(v, 3) for k, v in seconds.items()}))
     log("video: %d frames in %.2f s = %.1f frames/s stream to stream" % (frames, total, frames / max(total, 1e-9)))
     if model.redo_paths:

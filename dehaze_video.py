@@ -9,7 +9,8 @@
 The frame bytes go to the device as they are; YCbCr -> RGB, the forward and RGB -> YCbCr run there (cfen_vit_dehazing_amd/video.py,
 include/cfen_yuv.h).  Frames of the generator's size run as they are, any other size needs --fit or --tile.  With --out - the video leaves on
 stdout and everything printed goes to stderr.  --video_depth auto also takes streams of 9 to 16 bits per sample (C420p10, C444p12, ...), on a
-float route (include/cfen_yuv16.h); there other sizes need --tile.
+float route (include/cfen_yuv16.h); there other sizes need --tile.  --eval_gt CLEAR.y4m scores the stream that leaves against a ground-truth
+stream of the same geometry, per plane (PSNR, SSIM, a temporal error; include/cfen_planes.h), on every route, and writes gt.csv.
 """
 import os
 import sys
