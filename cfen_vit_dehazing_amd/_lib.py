@@ -194,6 +194,11 @@ HEADERS = {
         "cfen_motion_search_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
         "cfen_motion_warp": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     },
+    # sub-pixel motion compensation
+    "cfen_subpel.h": {
+        "cfen_motion_refine_u8": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+        "cfen_motion_warp_subpel": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    },
     # flicker along the motion
     "cfen_flicker.h": {
         "cfen_flicker_bytes": (c_size_t, [_I, _I, _I]),

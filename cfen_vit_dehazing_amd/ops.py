@@ -699,6 +699,48 @@ def motion_warp(vec, prev_guide, state, block, out=None):
     return prev_out, state_out
 
 
+def motion_refine_u8(guide, prev_guide, vec, block, subpel, bias, out=None):
+    """cfen_motion_refine_u8 (include/cfen_subpel.h): the whole-pixel block vectors vec (B,bh,bw,2) int16 of motion_search_u8 on the same guide
+    (B,h,w,3) uint8 and prev_guide (h,w,3) uint8, refined to 1 / subpel pixel (subpel 2 or 4) by an exhaustive search of the (2 subpel - 1)^2
+    bilinearly sampled positions within +-3/4 pixel, in one launch: returns (vec4 (B,bh,bw,2) int16 in QUARTER pixels, sad4 (B,bh,bw) int32, the
+    winner's SAD).  out: the caller's (vec4, sad4) pair."""
+    _rgb_batch("motion_refine_u8", guide=guide)
+    B, h, w, _ = guide.shape
+    dev = guide.device
+    _tensor_arg("motion_refine_u8", "prev_guide", prev_guide, (h, w, 3), torch.uint8, like=guide)
+    block = _motion_block("motion_refine_u8", block)
+    q = _int_arg("motion_refine_u8", "subpel", subpel, 2, 4, choices=(2, 4))
+    bi = _int_arg("motion_refine_u8", "bias", bias, 0, 255)
+    bh, bw = -(-h // block), -(-w // block)
+    _tensor_arg("motion_refine_u8", "vec", vec, (B, bh, bw, 2), torch.int16, like=guide)
+    vec4, sad4 = _pair(out)
+    vec4 = _out(vec4, (B, bh, bw, 2), torch.int16, dev, "motion_refine_u8")
+    sad4 = _out(sad4, (B, bh, bw), torch.int32, dev, "motion_refine_u8")
+    check(_lib.load().cfen_motion_refine_u8(ptr(guide), ptr(prev_guide), ptr(vec), B, h, w, block, q, bi, ptr(vec4), ptr(sad4), current_stream()),
+          "motion_refine_u8")
+    return vec4, sad4
+
+
+def motion_warp_subpel(vec4, prev_guide, state, block, out=None):
+    """cfen_motion_warp_subpel (include/cfen_subpel.h): motion_warp for vectors in quarter pixels: the previous frame prev_guide (h,w,3) uint8
+    sampled bilinearly in integers, and the recursion's state (h,w,6) float32 lerped in fp32, where each pixel's block vector vec4 (bh,bw,2) int16
+    of motion_refine_u8 points (tap coordinates clamped to the frame): returns (prev_out (h,w,3) uint8, state_out (h,w,6) float32).  Multiples of 4
+    give motion_warp with vec4 / 4.  Inputs and outputs must not overlap.  out: the caller's (prev_out, state_out) pair."""
+    _tensor_arg("motion_warp_subpel", "prev_guide", prev_guide, (None, None, 3), torch.uint8)
+    h, w, _ = prev_guide.shape
+    dev = prev_guide.device
+    block = _motion_block("motion_warp_subpel", block)
+    bh, bw = -(-h // block), -(-w // block)
+    _tensor_arg("motion_warp_subpel", "vec4", vec4, (bh, bw, 2), torch.int16, like=prev_guide)
+    _tensor_arg("motion_warp_subpel", "state", state, (h, w, 6), torch.float32, like=prev_guide)
+    prev_out, state_out = _pair(out)
+    prev_out = _out(prev_out, (h, w, 3), torch.uint8, dev, "motion_warp_subpel")
+    state_out = _out(state_out, (h, w, 6), torch.float32, dev, "motion_warp_subpel")
+    check(_lib.load().cfen_motion_warp_subpel(ptr(vec4), ptr(prev_guide), ptr(state), h, w, block, ptr(prev_out), ptr(state_out), current_stream()),
+          "motion_warp_subpel")
+    return prev_out, state_out
+
+
 def _image_pair(what, a, b):
     """the two images of a full-reference score as a batch: (a, b, u8, B, C, H, W)"""
     _cuda(a, b)

@@ -52,6 +52,11 @@ class VideoOptions(TestOptions):
                        help='--temporal_mc: preference for short vectors, in sixteenths of a level of mean absolute difference per pixel of displacement, '
                             '0 .. 255 (default 4). The defaults of the --temporal_mc options come from a synthetic panning experiment on the '
                             'scattering-model scene (DESIGN section 20), not from a checkpoint')
+        p.add_argument('--temporal_mc_subpel', type=int, default=None, choices=(1, 2, 4),
+                       help='--temporal_mc: refine the block vectors to 1/2 or 1/4 of a working-resolution pixel and fetch the previous frame and '
+                            'the state bilinearly (DESIGN section 25): the working resolution is 1 / --temporal_down of the frame, so a real pan '
+                            'is a fraction of a working pixel there (default 1 = whole pixels, the run without the flag). The evidence is the '
+                            'synthetic panning experiment of DESIGN section 25 on the scattering-model scene, not footage')
         p.add_argument('--eval_flicker', action='store_true',
                        help='(extension) score the flicker of the stream along the motion (DESIGN section 22): per frame pair, how much the '
                             "network's frames and the frames that leave change where the hazy input, followed along block vectors, did not; "
@@ -90,6 +95,21 @@ class VideoOptions(TestOptions):
     def _without_temporal_mc(text):
         """a run without --temporal_mc prints and records what it always did"""
         return ''.join(l for l in text.splitlines(True) if not l.startswith('temporal_mc'))
+
+    @staticmethod
+    def _without_temporal_mc_subpel(text):
+        """a run without --temporal_mc_subpel 2 or 4 prints and records what it always did"""
+        return ''.join(l for l in text.splitlines(True) if not l.startswith('temporal_mc_subpel'))
+
+    @staticmethod
+    def _check_temporal_mc_subpel(first):
+        """the refusals of --temporal_mc_subpel (what is none of 1, 2, 4 argparse itself refuses, with 2)"""
+        if first.temporal_mc_subpel is None:
+            return
+        if not first.temporal:
+            raise ValueError('--temporal_mc_subpel only applies with --temporal')
+        if not first.temporal_mc:
+            raise ValueError('--temporal_mc_subpel refines the vectors of --temporal_mc: it only applies with --temporal_mc > 0')
 
     def _check_temporal_mc(self, first):
         """the refusals of the --temporal_mc options; returns the defaults of those not given, as arguments"""
@@ -219,7 +239,9 @@ class VideoOptions(TestOptions):
             raise ValueError('--eval_gt %s: %s' % (first.eval_gt, e.strerror or e))
         depth_given = first.video_depth != '8'
         extra_temporal = self._check_temporal(first) + self._check_temporal_mc(first) + self._check_flicker(first)
+        self._check_temporal_mc_subpel(first)
         mc_on = bool(first.temporal and first.temporal_mc)
+        subpel_on = mc_on and (first.temporal_mc_subpel or 1) > 1
         # test.py's own checks run on what test.py would be given: frames in order, and --tile there means one image per call.  What that parse
         # prints and records is held back, corrected to the batch size this run really uses, and recorded in a file of its own: opt.txt stays
         # what the last test.py run of the same --name wrote
@@ -239,6 +261,7 @@ class VideoOptions(TestOptions):
         text = held.getvalue().replace('\nbatchSize: 1\n', '\nbatchSize: %d\n' % opt.batchSize) if first.tile else held.getvalue()
         text = text if first.temporal else self._without_temporal(text)
         text = text if mc_on else self._without_temporal_mc(text)
+        text = text if subpel_on else self._without_temporal_mc_subpel(text)
         text = text if first.eval_flicker else self._without_flicker(text)
         text = text if depth_given else self._without_video_depth(text)
         text = text if first.eval_gt else self._without_gt(text)
@@ -249,6 +272,7 @@ class VideoOptions(TestOptions):
                 recorded = open(opt_txt).read()
                 recorded = recorded if first.temporal else self._without_temporal(recorded)
                 recorded = recorded if mc_on else self._without_temporal_mc(recorded)
+                recorded = recorded if subpel_on else self._without_temporal_mc_subpel(recorded)
                 recorded = recorded if first.eval_flicker else self._without_flicker(recorded)
                 recorded = recorded if depth_given else self._without_video_depth(recorded)
                 recorded = recorded if first.eval_gt else self._without_gt(recorded)

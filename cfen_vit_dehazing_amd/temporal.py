@@ -6,7 +6,9 @@ resolution, smooths (a, b) over time by a recursion that a motion test switches 
 the full-resolution output by the CHANGE of the coefficients (ops.temporal_apply_u8): the network's own detail stays, and where nothing is
 smoothed the bytes are the network's.  With mc_range > 0 the recursion follows the scene (include/cfen_motion.h): each
 block of the working-resolution frame is looked up in the previous frame (ops.motion_search_u8), and the state and the previous frame are
-fetched from there (ops.motion_warp) before the same blend runs.  Everything runs on the current stream; nothing synchronises with the host."""
+fetched from there (ops.motion_warp) before the same blend runs.  With mc_subpel 2 or 4 the vectors are refined to half or quarter pixels
+(ops.motion_refine_u8) and the fetch is bilinear (ops.motion_warp_subpel; include/cfen_subpel.h): the working resolution is
+1 / down of the frame, so a real pan is a fraction of a working pixel.  Everything runs on the current stream; nothing synchronises with the host."""
 import math
 
 import torch
@@ -61,6 +63,23 @@ def check_mc_params(mc_range, mc_block, mc_bias, what="Stabiliser"):
     return tuple(out)
 
 
+# sub-pixel refinement of the block vectors (include/cfen_subpel.h): 1 = whole pixels, the path without; 2 and 4 = half and quarter pixels
+MC_SUBPEL = (1, 2, 4)
+
+
+def check_mc_subpel(mc_subpel, mc_range=None, what="Stabiliser"):
+    """mc_subpel as an int; ValueError unless it is 1, 2 or 4, and -- where mc_range is given -- unless refinement has vectors to refine"""
+    try:
+        i = int(mc_subpel)
+    except (TypeError, ValueError, OverflowError):
+        i = None
+    if i is None or i != mc_subpel or i not in MC_SUBPEL:
+        raise ValueError("%s: mc_subpel must be 1, 2 or 4, got %r" % (what, mc_subpel))
+    if i > 1 and mc_range is not None and not mc_range:
+        raise ValueError("%s: mc_subpel = %d refines the vectors of motion compensation: it needs mc_range > 0" % (what, i))
+    return i
+
+
 def working_size(H, W, down="auto"):
     """(S, h, w): the factor and the working resolution of H x W frames; auto is S = ceil(max(H, W) / 1024)"""
     S = -(-max(H, W) // 1024) if down == "auto" else int(down)
@@ -71,12 +90,15 @@ class Stabiliser:
     """step(hazy_u8, out_u8) for consecutive batches of consecutive frames, (n,H,W,3) uint8 CUDA tensors: the stabilised (n,H,W,3) uint8 frames.
     The first frame after construction or reset() passes unchanged.  The object owns the recursion's state, a copy of the last working-resolution
     hazy frame and its scratch tensors; the result does not depend on how the frames are grouped into batches.  mc_range > 0 (keyword only, with
-    mc_block and mc_bias): motion compensation, one search launch per batch and a warp and a one-frame blend per frame; 0 is the path without."""
+    mc_block and mc_bias): motion compensation, one search launch per batch and a warp and a one-frame blend per frame; 0 is the path without.
+    mc_subpel 2 or 4 (keyword only, needs mc_range > 0): one refine launch per batch after the search, and the sub-pixel warp; 1 is the path
+    without."""
 
     def __init__(self, radius=2, eps=1e-4, strength=0.8, motion=8.0, down="auto", *, mc_range=MC_DEFAULTS["range"], mc_block=MC_DEFAULTS["block"],
-                 mc_bias=MC_DEFAULTS["bias"]):
+                 mc_bias=MC_DEFAULTS["bias"], mc_subpel=MC_SUBPEL[0]):
         self.radius, self.eps, self.strength, self.motion, self.down = check_params(radius, eps, strength, motion, down)
         self.mc_range, self.mc_block, self.mc_bias = check_mc_params(mc_range, mc_block, mc_bias)
+        self.mc_subpel = check_mc_subpel(mc_subpel, self.mc_range)
         self.reset()
 
     def reset(self):
@@ -85,6 +107,7 @@ class Stabiliser:
         self._key = None
         self._state = self._prev = self._coef = self._delta = None
         self._state2 = self._warped = self._vec = self._sad = self._frame = None          # motion compensation: the second state, I^w, the batch's field
+        self._vec4 = self._sad4 = None                                                     # the batch's refined field
 
     def step(self, hazy_u8, out_u8, out=None):
         for name, t in (("hazy_u8", hazy_u8), ("out_u8", out_u8)):
@@ -123,7 +146,8 @@ class Stabiliser:
 
     def _blend_compensated(self, I, coef, n):
         """the compensated recursion of include/cfen_motion.h over the n frames I: one search for the batch, then per frame the warp into the
-        other state buffer and the one-frame blend on it, in place"""
+        other state buffer and the one-frame blend on it, in place.  mc_subpel > 1: the recursion of include/cfen_subpel.h, one refine after the
+        search and the sub-pixel warp in place of the warp"""
         _, h, w, _ = I.shape
         bh, bw = -(-h // self.mc_block), -(-w // self.mc_block)
         if self._state2 is None:
@@ -132,6 +156,9 @@ class Stabiliser:
         if self._vec is None or self._vec.shape[0] < n:
             self._vec = torch.empty(n, bh, bw, 2, dtype=torch.int16, device=I.device)
             self._sad = torch.empty(n, bh, bw, dtype=torch.int32, device=I.device)
+        if self.mc_subpel > 1 and (self._vec4 is None or self._vec4.shape[0] < n):
+            self._vec4 = torch.empty(n, bh, bw, 2, dtype=torch.int16, device=I.device)
+            self._sad4 = torch.empty(n, bh, bw, dtype=torch.int32, device=I.device)
         delta = self._delta[:n]
         first = 0 if self._have else 1                     # the first frame of a stream has no predecessor to search
         if not self._have:
@@ -139,8 +166,12 @@ class Stabiliser:
         if first < n:
             vec, _ = ops.motion_search_u8(I[first:], I[0] if first else self._prev, self.mc_block, self.mc_range, self.mc_bias,
                                           out=(self._vec[:n - first], self._sad[:n - first]))
+            if self.mc_subpel > 1:
+                vec, _ = ops.motion_refine_u8(I[first:], I[0] if first else self._prev, vec, self.mc_block, self.mc_subpel, self.mc_bias,
+                                              out=(self._vec4[:n - first], self._sad4[:n - first]))
+        warp = ops.motion_warp_subpel if self.mc_subpel > 1 else ops.motion_warp
         for k in range(first, n):
-            ops.motion_warp(vec[k - first], I[k - 1] if k else self._prev, self._state, self.mc_block, out=(self._warped, self._state2))
+            warp(vec[k - first], I[k - 1] if k else self._prev, self._state, self.mc_block, out=(self._warped, self._state2))
             ck, dk = coef[k:k + 1], delta[k:k + 1]
             aside = bool((k * h * w) % 2)                  # 24 k h w bytes into the batch: not the 16-byte boundary the blend asks for
             if aside:

@@ -417,14 +417,18 @@ def run(opt, log=print):
     if getattr(opt, "temporal", False):
         from . import temporal
         mc = getattr(opt, "temporal_mc", None) or 0
+        subpel = (getattr(opt, "temporal_mc_subpel", None) or 1) if mc else 1
         stabiliser = temporal.Stabiliser(opt.temporal_radius, opt.temporal_eps, opt.temporal_strength, opt.temporal_motion, opt.temporal_down,
-                                         **(dict(mc_range=mc, mc_block=opt.temporal_mc_block, mc_bias=opt.temporal_mc_bias) if mc else {}))
+                                         **(dict(mc_range=mc, mc_block=opt.temporal_mc_block, mc_bias=opt.temporal_mc_bias) if mc else {}),
+                                         **(dict(mc_subpel=subpel) if subpel > 1 else {}))
         S, h, w = temporal.working_size(H, W, stabiliser.down)
         log("video: temporal stabilisation at %d x %d (1/%d), radius %d, eps %g, strength %g, motion %g levels"
             % (w, h, S, stabiliser.radius, stabiliser.eps, stabiliser.strength, stabiliser.motion))
         if mc:
             log("video: motion compensation within +-%d pixels, blocks of %d x %d, bias %d / 16 levels per pixel"
                 % (stabiliser.mc_range, stabiliser.mc_block, stabiliser.mc_block, stabiliser.mc_bias))
+        if subpel > 1:
+            log("video: vectors refined to 1/%d pixel" % stabiliser.mc_subpel)
 
     scorer, flicker_rows = None, []
     if getattr(opt, "eval_flicker", False):
