@@ -209,6 +209,10 @@ HEADERS = {
         "cfen_plane_metrics_bytes": (c_size_t, [_I, _I, _I, _I]),
         "cfen_plane_metrics": (_I, [_P, c_size_t, _P, c_size_t, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     },
+    # LayerNorm over token rows with padding slots
+    "cfen_padnorm.h": {
+        "cfen_layernorm_padded": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, c_float, _P]),
+    },
 }
 SIGNATURES = HEADERS["cfen_hip.h"]          # the core table, by the name the frozen ABI's tests and documents use
 

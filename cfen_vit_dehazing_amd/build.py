@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcfen_hip.so")
-SOURCES = ["k_gemm.hip", "k_attention.hip", "k_tokens.hip", "k_conv.hip", "k_conv_tile.hip", "k_mlp.hip", "k_embed.hip", "k_lvit.hip", "k_stream.hip", "k_gvit.hip", "k_head5.hip", "k_fuse.hip", "k_tail.hip", "k_tile.hip", "k_ensemble.hip", "k_resample.hip", "k_guided.hip", "k_temporal.hip", "k_motion.hip", "k_subpel.hip", "k_flicker.hip", "k_metrics.hip", "k_planes.hip", "k_colordiff.hip", "k_noref.hip", "k_yuv.hip", "k_yuv16.hip", "k_png.hip", "k_dcn.hip", "k_dcn_bwd.hip", "cfen_api.cpp", "cfen_net.cpp", "cfen_tune.cpp"]
+SOURCES = ["k_gemm.hip", "k_attention.hip", "k_padnorm.hip","k_tokens.hip", "k_conv.hip", "k_conv_tile.hip", "k_mlp.hip", "k_embed.hip", "k_lvit.hip", "k_stream.hip", "k_gvit.hip", "k_head5.hip", "k_fuse.hip", "k_tail.hip", "k_tile.hip", "k_ensemble.hip", "k_resample.hip", "k_guided.hip", "k_temporal.hip", "k_motion.hip", "k_subpel.hip", "k_flicker.hip", "k_metrics.hip", "k_planes.hip", "k_colordiff.hip", "k_noref.hip", "k_yuv.hip", "k_yuv16.hip", "k_png.hip", "k_dcn.hip", "k_dcn_bwd.hip", "cfen_api.cpp", "cfen_net.cpp", "cfen_tune.cpp"]
 # per-file codegen flags.  k_attention: the softmax is VALU bound -- drop fmaxf's NaN canonicalisation (no NaNs can
 # occur: masked scores are -1e30, not -inf) and let MFMA results land in VGPRs instead of AGPR + v_accvgpr_read.
 EXTRA_FLAGS = {"k_attention.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],

@@ -691,7 +691,7 @@ struct cfen_net::VitCtx {
   int layernorm(const char* lname) const {   // YN = LayerNorm(X1)
     const float *lg[3], *lb[3];
     for (int g = 0; g < ng; ++g) { lg[g] = Pf(g, lname, ".g"); lb[g] = Pf(g, lname, ".b"); }
-    return cfen_layernorm_impl_g(dt, ng, X1, YN, lg, lb, M, v.D, 1e-5f, n.stream, v.Dn);
+    return cfen_layernorm_impl_g(dt, ng, X1, YN, lg, lb, M, v.D, 1e-5f, n.stream, v.Dn < v.D ? v.C : 0, v.Dn / (v.p * v.p));   // v5: C of v.C slots per pixel are real
   }
   // fused front half: weights "<name>.embed<sfx>" / ".qkv<sfx>", patch tokens gathered from `src` at channel stride cs
   CfenEmbedQkvArgs embed_qkv_args(int g, const char* sfx, const void* src, int cs, int hm_heads) const {

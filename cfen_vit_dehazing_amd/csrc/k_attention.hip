@@ -637,11 +637,16 @@ int dispatch_attn(int ng, const void* const* qkv, void* const* out, int nseq, in
 // LayerNorm over the last dim, statistics in fp32 (two passes over registers).  A row is handled by a
 // group of G = 16, 32 or 64 lanes (G >= D / (16-byte vector)), so a wave normalises 4 / 2 / 1 rows and all
 // lanes carry data even for the 192-byte rows of LViT level 1.
-// Dn <= D: the row's trailing / interleaved padding entries are exact zeros that do not belong to the normalised vector
-// (v5 LViT: 6- and 12-channel maps live at a channel stride of 8 / 16, so a token row carries zero slots); statistics are over
-// the Dn real entries, the padding slots get gamma = beta = 0 from the packer.
-template <typename T, int MAXV, int G>
-__global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg, PtrG<const float> gg, PtrG<const float> bg, int M, int D, float eps, int Dn) {
+// PAD (include/cfen_padnorm.h): the row is D / cs pixels of cs slots of which the first C are real; the other slots do not belong to the normalised
+// vector (v5 LViT: 6- and 12-channel maps live at a channel stride of 8 / 16, so a token row carries zero slots).  Statistics are over the
+// Dn = D / cs * C real entries.  A padding slot is never read into the arithmetic: it is held as an exact 0 AFTER centring, in both passes, so it
+// adds nothing to either sum and no correction term exists -- the earlier form centred the zero slots to -p like every other and took
+// (D - Dn) p and (D - Dn) (p + mean)^2 back out of the sums afterwards, which leaves a variance of the size of the spread as the difference of
+// two fp32 terms of the size of the mean squared (DESIGN 21 has what that cost, measured).  Its output is 0 * rstd * gamma + beta.
+// PAD = false is the code every unpadded row has always run.
+template <typename T, int MAXV, int G, bool PAD>
+__device__ __forceinline__ void layernorm_rows(const PtrG<const T>& Xg, const PtrG<T>& Yg, const PtrG<const float>& gg, const PtrG<const float>& bg, int M,
+                                               int D, float eps, int Dn, int cs, int C) {
   const T* __restrict__ X = Xg.p[blockIdx.z];
   T* __restrict__ Y = Yg.p[blockIdx.z];
   const float* __restrict__ g = gg.p[blockIdx.z];
@@ -658,18 +663,28 @@ __global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg,
   // rounding of the size of the mean itself (a row of 1 +- 0.01 lost a digit of its normalised values to the rounding of a sum near D)
   const float p = (float)x[0];
   float v[MAXV][EPL];
+  unsigned real[MAXV];                               // PAD: bit e = element e of vector i is a real slot (slot % cs < C); slot 0, where p comes from, always is
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
     int idx = gl + i * G;
+    real[i] = ~0u;
     if (idx < nvec) {
       Vec16<T>::load(x + idx * EPL, v[i]);
+      if constexpr (PAD) {
+        real[i] = 0u;
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) { v[i][e] -= p; sum += v[i][e]; }
+        for (int e = 0; e < EPL; ++e) real[i] |= (unsigned)((idx * EPL + e) % cs < C) << e;
+      }
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) {
+        v[i][e] -= p;
+        if constexpr (PAD) v[i][e] = (real[i] >> e & 1u) ? v[i][e] : 0.f;
+        sum += v[i][e];
+      }
     }
   }
   sum = group_sum<G>(sum);
-  sum += (float)(D - Dn) * p;                       // the zero slots each added 0 - p
   const float mean = sum / (float)Dn;               // of v - p
   float sq = 0.f;
 #pragma unroll
@@ -679,12 +694,12 @@ __global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg,
 #pragma unroll
       for (int e = 0; e < EPL; ++e) {
         float d = v[i][e] - mean;
+        if constexpr (PAD) v[i][e] = d = (real[i] >> e & 1u) ? d : 0.f;   // (the output pass reads the centred value back)
         sq += d * d;
       }
     }
   }
   sq = group_sum<G>(sq);
-  sq -= (float)(D - Dn) * (p + mean) * (p + mean);  // the zero slots each added (0 - p - mean)^2
   const float rstd = rsqrtf(fmaxf(sq, 0.f) / (float)Dn + eps);
   if (!live) return;
   T* y = Y + row * D;
@@ -694,18 +709,33 @@ __global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg,
     if (idx < nvec) {
       float o[EPL];
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) o[e] = (v[i][e] - mean) * rstd * g[idx * EPL + e] + b[idx * EPL + e];
+      for (int e = 0; e < EPL; ++e) o[e] = (PAD ? v[i][e] : v[i][e] - mean) * rstd * g[idx * EPL + e] + b[idx * EPL + e];
       Vec16<T>::store(y + idx * EPL, o);
     }
   }
 }
 
+template <typename T, int MAXV, int G>
+__global__ __launch_bounds__(256) void k_layernorm(PtrG<const T> Xg, PtrG<T> Yg, PtrG<const float> gg, PtrG<const float> bg, int M, int D, float eps) {
+  layernorm_rows<T, MAXV, G, false>(Xg, Yg, gg, bg, M, D, eps, D, 0, 0);
+}
+template <typename T, int MAXV, int G>
+__global__ __launch_bounds__(256) void k_layernorm_padded(PtrG<const T> Xg, PtrG<T> Yg, PtrG<const float> gg, PtrG<const float> bg, int M, int D, float eps,
+                                                          int cs, int C) {
+  layernorm_rows<T, MAXV, G, true>(Xg, Yg, gg, bg, M, D, eps, D / cs * C, cs, C);
+}
+
+// cs = 0: every slot of a row is real.  cs > 0: rows of D / cs pixels whose first C of cs slots are real (C = cs: no padding, the plain kernel)
 template <typename T, int MAXV>
-int launch_ln(int ng, const void* const* X, void* const* Y, const float* const* g, const float* const* b, int M, int D, float eps, hipStream_t s, int Dn) {
+int launch_ln(int ng, const void* const* X, void* const* Y, const float* const* g, const float* const* b, int M, int D, float eps, hipStream_t s, int cs, int C) {
   constexpr int EPL = Vec16<T>::N;
   CFEN_CHECK_ARG(M > 0 && D > 0, "layernorm: empty problem");
-  if (Dn <= 0) Dn = D;
-  CFEN_CHECK_ARG(Dn <= D, "layernorm: %d real entries in rows of %d", Dn, D);
+  CFEN_CHECK_ARG(cs >= 0, "layernorm: %d slots per pixel", cs);
+  if (cs > 0) {
+    CFEN_CHECK_ARG(C >= 1 && C <= cs, "layernorm: %d real slots per pixel of %d", C, cs);
+    CFEN_CHECK_ARG(D % cs == 0, "layernorm: rows of %d slots are no whole number of pixels of %d", D, cs);
+  }
+  const bool padded = cs > 0 && C < cs;
   CFEN_CHECK_ARG(D % EPL == 0 && D <= 64 * MAXV * EPL, "layernorm: D=%d unsupported (multiple of %d, <= %d)", D, EPL, 64 * MAXV * EPL);
   CFEN_CHECK_ARG(ng >= 1 && ng <= CFEN_MAX_GROUPS, "layernorm: 1..%d problems per launch", CFEN_MAX_GROUPS);
   PtrG<const T> xg{};
@@ -716,12 +746,20 @@ int launch_ln(int ng, const void* const* X, void* const* Y, const float* const* 
     xg.p[k] = (const T*)X[k]; yg.p[k] = (T*)Y[k]; gg.p[k] = g[k]; bg.p[k] = b[k];
   }
   const int nvec = D / EPL;
-  if (nvec <= 16) {
-    CFEN_LAUNCH((k_layernorm<T, 1, 16>), dim3((M + 15) / 16, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps, Dn);
+  if (padded) {
+    if (nvec <= 16) {
+      CFEN_LAUNCH((k_layernorm_padded<T, 1, 16>), dim3((M + 15) / 16, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps, cs, C);
+    } else if (nvec <= 32) {
+      CFEN_LAUNCH((k_layernorm_padded<T, 1, 32>), dim3((M + 7) / 8, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps, cs, C);
+    } else {
+      CFEN_LAUNCH((k_layernorm_padded<T, MAXV, 64>), dim3((M + 3) / 4, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps, cs, C);
+    }
+  } else if (nvec <= 16) {
+    CFEN_LAUNCH((k_layernorm<T, 1, 16>), dim3((M + 15) / 16, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps);
   } else if (nvec <= 32) {
-    CFEN_LAUNCH((k_layernorm<T, 1, 32>), dim3((M + 7) / 8, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps, Dn);
+    CFEN_LAUNCH((k_layernorm<T, 1, 32>), dim3((M + 7) / 8, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps);
   } else {
-    CFEN_LAUNCH((k_layernorm<T, MAXV, 64>), dim3((M + 3) / 4, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps, Dn);
+    CFEN_LAUNCH((k_layernorm<T, MAXV, 64>), dim3((M + 3) / 4, 1, ng), dim3(256), 0, s, xg, yg, gg, bg, M, D, eps);
   }
   CFEN_CHECK_LAUNCH("layernorm");
   return CFEN_OK;
@@ -771,12 +809,12 @@ int cfen_attention_impl(int dtype, const void* qkv, void* out, int nseq, int S, 
 }
 
 int cfen_layernorm_impl_g(int dtype, int ng, const void* const* X, void* const* Y, const float* const* g, const float* const* b, int M, int D,
-                          float eps, hipStream_t s, int Dn) {
-  if (dtype == 1) return launch_ln<half_t, 4>(ng, X, Y, g, b, M, D, eps, s, Dn);
-  if (dtype == 0) return launch_ln<float, 8>(ng, X, Y, g, b, M, D, eps, s, Dn);
+                          float eps, hipStream_t s, int cs, int C) {
+  if (dtype == 1) return launch_ln<half_t, 4>(ng, X, Y, g, b, M, D, eps, s, cs, C);
+  if (dtype == 0) return launch_ln<float, 8>(ng, X, Y, g, b, M, D, eps, s, cs, C);
   cfen_set_error("layernorm: unknown dtype %d", dtype);
   return CFEN_ERR_ARG;
 }
 int cfen_layernorm_impl(int dtype, const void* X, void* Y, const float* g, const float* b, int M, int D, float eps, hipStream_t s) {
-  return cfen_layernorm_impl_g(dtype, 1, &X, &Y, &g, &b, M, D, eps, s, 0);
+  return cfen_layernorm_impl_g(dtype, 1, &X, &Y, &g, &b, M, D, eps, s, 0, 0);
 }

@@ -230,9 +230,16 @@ def gemm_chain(phases, M, team=48, fold=None, sync=None):
     return int(sync[:8].view(torch.int32)[1].item()) if own else None     # with a caller-owned `sync` buffer: no read-back (word 1 of it = error)
 
 
-def layernorm(x, gamma, beta, eps=1e-5, out=None):
+def layernorm(x, gamma, beta, eps=1e-5, out=None, padded=None):
+    """LayerNorm over the rows of x (M, D).  padded = (cs, C): cfen_layernorm_padded of include/cfen_padnorm.h -- a row is D / cs pixels of cs
+    slots of which the first C are real; statistics over the real slots, the others come out as beta"""
     _cuda(x, gamma, beta)
     out = _out(out, x.shape, x.dtype, x.device, "layernorm")
+    if padded is not None:
+        cs, C = padded
+        check(_lib.load().cfen_layernorm_padded(dtype_code(x.dtype), ptr(x), ptr(out), ptr(gamma), ptr(beta), x.shape[0], x.shape[1], int(cs), int(C),
+                                                eps, current_stream()), "layernorm_padded")
+        return out
     check(_lib.load().cfen_layernorm(dtype_code(x.dtype), ptr(x), ptr(out), ptr(gamma), ptr(beta), x.shape[0], x.shape[1], eps,
                                      current_stream()), "layernorm")
     return out

@@ -226,24 +226,26 @@ def pack_vit_shrunk(sd, g, dtype):
     a = torch.arange(D)
     apos = (a // dh) * dhp + a % dh                                # slot of attention feature a
     e = n + ".encoder.layers.0"
-    f32 = torch.float32
+    # dtype float64 (no kernel takes it: tests/test_pack_shrunk_host.py applies the packed matrices in double) scatters, scales W_q and keeps the
+    # vectors in double; every other dtype goes through float32 as the kernels' operands always have
+    wk = torch.float64 if dtype == torch.float64 else torch.float32
     dev = sd[n + ".linear_encoding.weight"].device
     pos, apos = pos.to(dev), apos.to(dev)
 
     def mat(w, rows, nrows, cols, ncols):
-        out = torch.zeros(nrows, ncols, dtype=torch.float32, device=dev)
+        out = torch.zeros(nrows, ncols, dtype=wk, device=dev)
         r = rows if rows is not None else torch.arange(nrows, device=dev)
         cidx = cols if cols is not None else torch.arange(ncols, device=dev)
-        out[r[:, None], cidx[None, :]] = w.float()
+        out[r[:, None], cidx[None, :]] = w.to(wk)
         return out.to(dtype).contiguous()
 
     def vec(v, idx, nrows):
-        out = torch.zeros(nrows, dtype=f32, device=dev)
-        out[idx] = v.float()
+        out = torch.zeros(nrows, dtype=wk, device=dev)
+        out[idx] = v.to(wk)
         return out
 
-    w_in = sd[e + ".self_attn.in_proj_weight"].float()
-    qkv = torch.zeros(3 * Da, Dp, dtype=torch.float32, device=dev)
+    w_in = sd[e + ".self_attn.in_proj_weight"].to(wk)
+    qkv = torch.zeros(3 * Da, Dp, dtype=wk, device=dev)
     for t in range(3):
         blk = w_in[t * D:(t + 1) * D] * (math.sqrt(dhp / dh) if t == 0 else 1.0)
         qkv[(t * Da + apos)[:, None], pos[None, :]] = blk
@@ -254,9 +256,9 @@ def pack_vit_shrunk(sd, g, dtype):
         n + ".qkv.w": qkv.to(dtype).contiguous(),
         n + ".proj.w": mat(sd[e + ".self_attn.out_proj.weight"], pos, Dp, apos, Da),
         n + ".ln2.g": vec(sd[e + ".norm2.weight"], pos, Dp), n + ".ln2.b": vec(sd[e + ".norm2.bias"], pos, Dp),
-        n + ".ffn1.w": mat(sd[e + ".linear1.weight"], None, H, pos, Dp), n + ".ffn1.b": sd[e + ".linear1.bias"].to(f32),
+        n + ".ffn1.w": mat(sd[e + ".linear1.weight"], None, H, pos, Dp), n + ".ffn1.b": sd[e + ".linear1.bias"].to(wk),
         n + ".ffn2.w": mat(sd[e + ".linear2.weight"], pos, Dp, None, H), n + ".ffn2.b": vec(sd[e + ".linear2.bias"], pos, Dp),
-        n + ".head1.w": mat(sd[n + ".mlp_head.0.weight"], None, H, pos, Dp), n + ".head1.b": sd[n + ".mlp_head.0.bias"].to(f32),
+        n + ".head1.w": mat(sd[n + ".mlp_head.0.weight"], None, H, pos, Dp), n + ".head1.b": sd[n + ".mlp_head.0.bias"].to(wk),
         n + ".head2.w": mat(sd[n + ".mlp_head.3.weight"], pos, Dp, None, H), n + ".head2.b": vec(sd[n + ".mlp_head.3.bias"], pos, Dp),
     }
 

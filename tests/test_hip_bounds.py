@@ -230,6 +230,31 @@ def test_layernorm(dtype, M, D):
     close(y, cfen_oracle.layer_norm(x.double(), g.double(), b.double()), tol(dtype, 4))
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,cs,C", [(5, 8, 6), (33, 16, 12)])
+def test_guard_bands_padnorm(dtype, M, cs, C):
+    """include/cfen_padnorm.h through the C ABI: rows of 4 pixels of cs slots, C of them real, the padding slots of x NaN (they are never read into a
+    result); the padding slots of y come out as beta = 0.  Then four refused calls: y keeps its prefill"""
+    import padnorm_ref as pr
+    lib = _lib.load()
+    D, real = 4 * cs, pr.real_slots(cs, C)
+    x = pr.scatter(rnd((M, 4 * C), 1, dtype, 2.0) + 0.5, cs, C, fill=float("nan"))
+    g, b = pr.scatter(1 + 0.1 * rnd((4 * C,), 2, torch.float32), cs, C), pr.scatter(0.1 * rnd((4 * C,), 3, torch.float32), cs, C)
+    ins = [G(x, "x"), G(g, "gamma"), G(b, "beta")]
+    y = O((M, D), dtype, "y")
+    call = lambda M_, D_, cs_, C_: lib.cfen_layernorm_padded(_lib.dtype_code(dtype), ptr(ins[0]), ptr(y), ptr(ins[1]), ptr(ins[2]), M_, D_, cs_, C_, 1e-5,
+                                                             current_stream())
+    for bad in ((M, D, cs, cs + 1), (M, D, cs, 0), (M, D + 8, 16, C), (0, D, cs, C)):
+        assert call(*bad) == -1 and b"layernorm" in lib.cfen_last_error(), bad
+    bands(y, *ins)
+    assert bool((raw_bytes(y) == 255).all()), "a refused call wrote its output"
+    check(call(M, D, cs, C), "layernorm_padded")
+    bands(y, *ins)
+    on = real.to(y.device)
+    close(y[:, on], cfen_oracle.layer_norm(x[:, real].double(), g[real].double(), b[real].double()), tol(dtype, 4))
+    assert bool((y[:, ~on] == 0).all()), "padding slots are not beta = 0"
+
+
 # head dims 4 and 12 run in fp32 only (fragment width 4, not fp16's 8)
 ATTENTION = [(dt,) + c for dt in DTYPES for c in ((2, 1, 16, 24), (2, 4, 8, 24), (3, 256, 4, 24), (2, 16, 4, 8), (2, 80, 1, 128))] + \
             [(torch.float32, 3, 16, 4, 4), (torch.float32, 2, 64, 8, 12)]

@@ -45,8 +45,9 @@ def make_net(cfg, dtype, seed=0, mode="trained", sd=None):
 
 
 def fp32_stage_bar(name):
-    """sampled max-abs bar of the fp32 stages against a fixture: the 64-pixel v3 fixtures hold 2e-4, the full-size ones and the sibling generators 3e-4"""
-    return 3e-4 if name.startswith("full512") or name.split("_")[0] in ("cfs", "crs", "v5") else 2e-4
+    """sampled max-abs bar of the fp32 stages against a fixture: the 64-pixel v3 fixtures and both v5 fixtures hold 2e-4 (v5: worst stage 4.3e-6 at
+    128 x 128 and 4.1e-6 at 512 x 512 on an MI355X), the full-size v3 one and the cfs / crs generators 3e-4"""
+    return 3e-4 if name.startswith("full512") or name.split("_")[0] in ("cfs", "crs") else 2e-4
 
 
 def check_fp32_fixture(name, net, z, outs):

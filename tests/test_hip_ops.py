@@ -1243,3 +1243,116 @@ def test_attention_fp32_only_head_dims(dh):
     for S, heads, nseq in ((1, 16, 2), (16, 4, 3), (64, 8, 2), (256, 4, 2)):
         qkv = rnd((nseq * S, 3 * heads * dh), 7 + S, torch.float32, 1.5)
         close(ops.attention(qkv.to(dev()), nseq, S, heads), attn_ref(qkv, nseq, S, heads), tol(torch.float32, 3), "S %d dh %d" % (S, dh))
+
+
+# ---------------------------------------------------------------------------------------------------
+# the padded token rows of the v5 LViT blocks (include/cfen_padnorm.h, packing.pack_vit_shrunk)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cs,C", [(8, 6), (16, 12)])
+@pytest.mark.parametrize("M", [5, 33])
+def test_layernorm_padded_rows(dtype, M, cs, C):
+    """rows of 4 pixels of cs slots of which C are real, at test_layernorm's values and bar: statistics over the real slots only (what the padding
+    slots of x hold is not used: zeros in one run, NaN in the other, the same bits out), padding slots of the output exactly beta = 0, rows of the
+    output past M untouched"""
+    import padnorm_ref as pr
+    real = pr.real_slots(cs, C)
+    xr = rnd((M, 4 * C), 1, dtype, 2.0) + 0.5
+    g, b = pr.scatter(1 + 0.1 * rnd((4 * C,), 2, torch.float32), cs, C), pr.scatter(0.1 * rnd((4 * C,), 3, torch.float32), cs, C)
+    want = cfen_oracle.layer_norm(xr.double(), g[real].double(), b[real].double())
+    outs = []
+    for fill in (0.0, float("nan")):
+        out = torch.full((M + 3, 4 * cs), float("nan"), dtype=dtype, device=dev())
+        ops.layernorm(pr.scatter(xr, cs, C, fill).to(dev()), g.to(dev()), b.to(dev()), out=out[:M], padded=(cs, C))
+        out = out.cpu()
+        close(out[:M][:, real], want, tol(dtype, 4), "padding slots of x %r" % fill)
+        assert bool((out[:M][:, ~real] == 0).all()), "padding slots of the output are not beta = 0"
+        assert bool(torch.isnan(out[M:]).all()), "rows past M were written"
+        outs.append(out[:M])
+    assert torch.equal(outs[0], outs[1])
+    # no padding (C = cs) is cfen_layernorm, bit for bit
+    x = rnd((M, 4 * cs), 4, dtype, 2.0) + 0.5
+    g1 = (1 + 0.1 * rnd((4 * cs,), 5, torch.float32)).to(dev())
+    assert torch.equal(ops.layernorm(x.to(dev()), g1, g1, padded=(cs, cs)), ops.layernorm(x.to(dev()), g1, g1))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C,cs,heads", [(6, 8, 4), (12, 16, 8), (24, 24, 16)])
+def test_v5_block_on_the_padded_layout(dtype, C, cs, heads):
+    """a v5 LViT block from the operators the launch plan's unfused route launches (csrc/cfen_net.cpp vit_front / vit_attention / vit_back with
+    Vit::shrink), on pack_vit_shrunk weights and a (B, H, W, cs) map whose padding lanes are zero, against cfen_oracle.vit_tokens in float64 on
+    the real layout.  fp32 bar: BAR_FACTOR x the distance of a float32 run of vit_tokens from its float64 run; fp16 bar: FP16_STAGE_MARGIN x the
+    error of vit_tokens(quant=fp16 stores).  Padding slots are exact zeros after every operator.  offset 64: the embedding bias raised by 64 of
+    the embedded rows' spreads, which rides through the residual stream into norm1 and norm2 -- the padded LayerNorm's value edge inside a block."""
+    import value_edges_ref as ve
+    from helpers import FP16_STAGE_MARGIN
+    from test_pack_shrunk_host import block_weights, geometry, token_slots
+    d = dev()
+    g = geometry(C)
+    assert g.heads == heads and packing.cs_of(C) == cs
+    p, ws, B, H, W = g.patch, 8, 1, 8, 24                   # three windows of 16 tokens
+    n, dhp = g.name, packing.round_up(g.dim // heads, 8)
+    base = block_weights(g, dtype=dtype)
+    x = rnd((B, C, H, W), 11, dtype)
+    tok64 = cfen_oracle.unfold_tokens(cfen_oracle.window_partition(x.double(), ws), p)
+    taps = {}
+    cfen_oracle.vit_tokens({k: v.double() for k, v in base.items()}, n, tok64, heads, taps=taps)
+    spread = float(taps["embed"].std(-1).mean())
+    slots = token_slots(g, cs)
+    pad = torch.ones(p * p * cs, dtype=torch.bool)
+    pad[slots] = False
+    hpad = torch.arange(heads * dhp) % dhp >= g.dim // heads
+
+    def zero(t, m, what):
+        assert bool((t[:, m.to(d)] == 0).all()), "%s: a padding slot is not an exact zero" % what
+    ratios = {}
+    for rho in (0, 64):
+        sd = dict(base)
+        sd[n + ".linear_encoding.bias"] = (base[n + ".linear_encoding.bias"].double() + rho * spread).to(dtype)
+        sd64 = {k: v.double() for k, v in sd.items()}
+        exact = cfen_oracle.vit_tokens(sd64, n, tok64, heads)
+        if dtype == torch.float32:
+            model = cfen_oracle.vit_tokens(sd, n, tok64.float(), heads).double()
+            bar = ve.BAR_FACTOR * float((model - exact).abs().max())
+        else:
+            model = cfen_oracle.vit_tokens(sd64, n, tok64, heads, quant=lambda t: t.to(dtype).double())
+            bar = FP16_STAGE_MARGIN * float((model - exact).abs().max())
+        pk = {k: v.to(d).contiguous() for k, v in packing.pack_vit_shrunk(sd, g, dtype).items()}
+        P = lambda k: pk[n + k]
+        fmap = ops.to_nhwc(x, cs=cs).to(d)
+        t0 = ops.patchify(fmap, cs, ws, p)
+        zero(t0, pad, "patchify")
+        x1 = ops.gemm_nt(t0, P(".embed.w"), bias=P(".embed.b"), residual=t0, pos=P(".pos"))
+        zero(x1, pad, "embed")
+        if cs == C:
+            yn = ops.layernorm(x1, P(".ln1.g"), P(".ln1.b"))
+        else:
+            yn = ops.layernorm(x1, P(".ln1.g"), P(".ln1.b"), padded=(cs, C))
+            zero(yn, pad, "norm1")
+        qkv = ops.gemm_nt(yn, P(".qkv.w"))
+        zero(qkv, torch.cat([hpad] * 3), "qkv")
+        att = ops.attention(qkv, B * (H // ws) * (W // ws), g.seq, heads)
+        zero(att, hpad, "attention")
+        x2 = ops.gemm_nt(att, P(".proj.w"), residual=x1)
+        zero(x2, pad, "proj")
+        if cs == C:
+            yn = ops.layernorm(x2, P(".ln2.g"), P(".ln2.b"))
+        else:
+            yn = ops.layernorm(x2, P(".ln2.g"), P(".ln2.b"), padded=(cs, C))
+            zero(yn, pad, "norm2")
+        hid = ops.gemm_nt(yn, P(".ffn1.w"), bias=P(".ffn1.b"), relu=True)
+        x3 = ops.gemm_nt(hid, P(".ffn2.w"), bias=P(".ffn2.b"), residual=x2)
+        zero(x3, pad, "ffn2")
+        hid = ops.gemm_nt(x3, P(".head1.w"), bias=P(".head1.b"), relu=True)
+        x4 = ops.gemm_nt(hid, P(".head2.w"), bias=P(".head2.b"), residual=x3)
+        zero(x4, pad, "head2")
+        out = ops.unpatchify(x4, B, H, W, cs, cs, ws, p)
+        if cs > C:
+            assert bool((out[..., C:] == 0).all()), "unpatchify: a padding lane is not an exact zero"
+        got = ops.from_nhwc(out, C).double().cpu()
+        assert bool(torch.isfinite(got).all())
+        want = cfen_oracle.window_merge(cfen_oracle.fold_tokens(exact, C, ws, ws, p), B, H, W)
+        err = float((got - want).abs().max())
+        print("v5 block (C %d, cs %d, heads %d) %s offset %d: max-abs %.3e, bar %.3e" % (C, cs, heads, str(dtype).replace("torch.", ""), rho, err, bar))
+        ratios["offset%d" % rho] = err / bar
+    bad = {k: v for k, v in ratios.items() if not v <= 1.0}
+    assert not bad, "v5 block (C %d, cs %d) %s: error / bar above 1: %r" % (C, cs, dtype, bad)

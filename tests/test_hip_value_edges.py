@@ -373,3 +373,25 @@ def test_actnorm_device_init_value_edges(monkeypatch):
         print("actnorm init %s (rho %.1f): weight error %.3e, bar %.3e; bias error %.3e, bar %.3e" % (conv, rho, dw, bar_w, db, bar_b))
         ratios[conv + " weight"], ratios[conv + " bias"] = dw / bar_w, db / bar_b
     _report("actnorm init", torch.float32, ratios)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the padded token rows of the v5 LViT blocks (include/cfen_padnorm.h): the same cases over the real slots of a row, yardstick in padnorm_ref.py
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cs,C", [(8, 6), (16, 12)])
+def test_layernorm_padded_value_edges(dtype, cs, C):
+    """every case over the real slots of rows of 4 pixels of cs slots.  fp32, measured on an MI355X (error / bar):
+                               rho0   rho1   rho8    rho64    rho256   tiny_std  constant  alt_sign
+      (8, 6)   correction      0.336  0.288  0.0853  5.42     19.6     5.55      0         5.42      (zero slots centred to -p, taken back out of the sums)
+      (8, 6)   as shipped      0.311  0.288  0.0688  0.00777  0.00244  0.00675   0         0.00777   (a padding slot is 0 after centring, no correction)
+      (16, 12) correction      0.282  0.199  0.0698  0.078    19.5     5.96      0         0.0487
+      (16, 12) as shipped      0.276  0.163  0.0565  0.00951  0.00253  0.00745   0         0.0105
+    fp16 with the correction formula: rho256 1.48 / 4.57, everything else under 1 (DESIGN 21 has the whole table)."""
+    import padnorm_ref as pr
+    d = dev()
+    ratios = {}
+    for case in ve.CASES:
+        x, g, b, want, e32 = pr.yardstick(case, 33, cs, C, dtype)
+        ratios[case] = ve.ratio(ops.layernorm(x.to(d), g.to(d), b.to(d), padded=(cs, C)), want, e32, dtype)
+    assert set(ratios) == set(ve.CASES)
+    _report("layernorm padded (cs %d, C %d)" % (cs, C), dtype, ratios)
